@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - env-steps/s of the batched MiniWorld hot path on N MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +11,10 @@ region.  For N > 1 every rank owns a contiguous env range (weak scaling: envs pe
 rank 0 (the "learner") scatters the actions, and every rank's observation shard + reward / done / info
 pack is exchanged in one round (RCCL), overlapped with the next step and consumed one round behind
 inside the timed loop.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline figure.  --full adds everything else: the
+per-kernel times and the roofline (HIP events inside the timed region), the multi-rank exchange self-check, the leg
+through the VecEnv boundary and the CPU oracle baseline.  --dump-outputs DIR writes what the last timed step returned.
 """
 import argparse
 import json
@@ -53,6 +57,8 @@ ORACLE_TASK = {"MiniWorld-Maze-v0": ("Maze", None), "MiniWorld-OneRoom-v0": ("On
                "MiniWorld-CollectHealth-v0": ("CollectHealth", [16, 0, 0, 0]), "MiniWorld-Sidewalk-v0": ("Sidewalk", None)}
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 ACTION_SEED = 12345
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs stays under 64 MB in all, .npy headers included
+DUMP_SEED = 0
 
 
 def splitmix64(x):
@@ -187,6 +193,31 @@ def load_traffic(workload):
     return None
 
 
+def dump_outputs(env, out_dir):
+    """What a caller of BatchedMiniWorld.step holds after the last timed step, as out_dir/<name>.npy: reward (float64),
+    done, ep_steps, feature, goal_pos of every env (float64, exact), and obs (and depth) as float32 for a fixed, seeded
+    sample of envs (sample_env_index) sized to keep the dump within DUMP_BYTES."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    out = {k: getattr(env, k).cpu().numpy().astype(np.float64)
+           for k in ("reward64", "done", "ep_steps", "feature", "goal_pos")}
+    out["reward"] = out.pop("reward64")
+    big = {"obs": env.obs}
+    if env.depth is not None:
+        big["depth"] = env.depth
+    n = env.num_envs
+    per_env = sum(t[0].numel() for t in big.values()) * 4 + 8
+    k = min(n, (DUMP_BYTES - sum(a.nbytes for a in out.values())) // per_env)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    out["sample_env_index"] = idx.astype(np.float64)
+    sel = torch.from_numpy(idx).to(env.device)
+    for name, t in big.items():
+        out[name] = t.index_select(0, sel).cpu().numpy().astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -194,8 +225,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", default="maze8192", choices=sorted(WORKLOADS))
     ap.add_argument("--envs-per-gpu", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-vecenv", action="store_true", help="skip the (untimed-for-`value`) leg through the VecEnv boundary")
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel times + roofline, the multi-rank exchange self-check, the VecEnv leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32 / float64; rank 0's shard)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-vecenv", action="store_true", help="with --full: skip the (untimed-for-`value`) leg through the VecEnv boundary")
     ap.add_argument("--no-gather", action="store_true", help="skip the obs all-gather for N > 1")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend; gloo (+ --no-gather) only to rehearse the multi-rank flow on one GPU")
@@ -204,6 +239,8 @@ def main():
                     help="method of the per-step shard exchange (auto: time ring and direct in the warm-up, keep the faster; "
                          "learner: only rank 0 receives the batch - 1/N of the bytes an all-gather moves)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -265,7 +302,7 @@ def main():
 
     run(0, Wm)
     multi = None
-    if gather is not None and Wm > 0:
+    if args.full and gather is not None and Wm > 0:
         # self-check, outside the timed region: every rank's shard of the newest round arrived where the method delivers it
         # (per-shard checksums, all-gathered separately), on distinct devices, and what one exchange costs unoverlapped
         gather.latest()
@@ -284,17 +321,21 @@ def main():
         if not ok or seen != world:
             sys.exit("bench.py: the shard exchange did not deliver every rank's shard (%r)" % (multi,))
     fence()
-    # HIP events on the launch stream, every 4th step of the timed region whatever its length (seven events per step
-    # cost ~2-5 % of a step's time); read back only after the timed region
-    env.timing_enable(4 if K >= 4 else True)
+    # --full: HIP events on the launch stream, every 4th step of the timed region whatever its length (seven events per
+    # step cost ~2-5 % of a step's time); read back only after the timed region
+    if args.full:
+        env.timing_enable(4 if K >= 4 else True)
     t_start = time.perf_counter()
     run(Wm, Wm + K)
     if gather is not None:
         gather.drain()
     fence()
     elapsed = time.perf_counter() - t_start
-    kt = env.timing_read()
-    env.timing_enable(False)
+    if args.full:
+        kt = env.timing_read()
+        env.timing_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -302,8 +343,6 @@ def main():
 
     if rank == 0:
         value = total * K / elapsed
-        render_ms = kt["render"]
-        achieved = alg_bytes * count / (render_ms * 1e-3) / 1e9 if render_ms > 0 else 0.0
         out = {
             "metric": "env-steps/s (80x60 RGB obs)", "value": value, "unit": "env-steps/s", "n_gpus": world,
             "steps": K, "warmup": Wm, "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -313,24 +352,27 @@ def main():
                        "actions": "uniform random over %s, counter-based" % ("{turn_left, turn_right, move_forward}" if n_actions == 3 else "the %d actions of the task" % n_actions),
                        "auto_reset": True, "parallelism": "env-sharded x%d%s" % (world, "" if gather is None else " + per-step exchange(obs u8 + aux f64[8], %s) + action scatter" % gather.method),
                        "gather_tuning_s": None if gather is None else gather.tuned},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": load_traffic(args.workload),
-                         "traffic_source": "committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload (profiles/r*_pmc_traffic.json, scripts/profile_workload.sh); not re-measured in this run",
-                         "kernel": "render_kernel", "kernel_ms": render_ms,
-                         "algorithmic_bytes_per_launch": alg_bytes * count,
-                         "note": "nominally HBM-bound path; the practical limiter is VALU issue (DESIGN.md 4: issue-slot accounting from the committed SQ counter passes)"},
-            "kernel_ms": {k: kt[k] for k in ("step", "reset", "prep", "render")},
         }
+        if args.full:
+            render_ms = kt["render"]
+            achieved = alg_bytes * count / (render_ms * 1e-3) / 1e9 if render_ms > 0 else 0.0
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": load_traffic(args.workload),
+                               "traffic_source": "committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload (profiles/r*_pmc_traffic.json, scripts/profile_workload.sh); not re-measured in this run",
+                               "kernel": "render_kernel", "kernel_ms": render_ms,
+                               "algorithmic_bytes_per_launch": alg_bytes * count,
+                               "note": "nominally HBM-bound path; the practical limiter is VALU issue (DESIGN.md 4: issue-slot accounting from the committed SQ counter passes)"}
+            out["kernel_ms"] = {k: kt[k] for k in ("step", "reset", "prep", "render")}
         if multi is not None:
             out["multi_gpu"] = multi
-        if world == 1 and not args.no_vecenv:
+        if args.full and world == 1 and not args.no_vecenv:
             env.close()
             try:
                 out["vecenv"] = vecenv_rates(env_id, per_gpu, dr, device, K, Wm, n_actions)
                 out["vecenv"]["vs_c_abi"] = out["vecenv"]["vecenv_u8"]["value"] / value
             except Exception as ex:
                 out["vecenv"] = {"error": repr(ex)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(env_id, depth, dr, n_actions=n_actions)
             except Exception as ex:   # the oracle is only a reported baseline; never fail the GPU number on it

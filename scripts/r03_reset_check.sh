@@ -5,8 +5,8 @@ timeout -k 10 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_ymaze
 echo "tests rc=$?"; tail -3 $out/tests.log
 timeout -k 10 120 python scripts/mass_timeout.py > $out/mass.txt 2>&1; tail -1 $out/mass.txt
 timeout -k 10 120 python scripts/mass_timeout.py MiniWorld-FourRooms-v0 > $out/mass_fr.txt 2>&1; tail -1 $out/mass_fr.txt
-timeout -k 10 200 python bench.py --steps 300 --warmup 50 --no-vecenv --no-cpu-baseline > $out/bench300.json 2>/dev/null
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-vecenv --no-cpu-baseline > $out/bench20.json 2>/dev/null
+timeout -k 10 200 python bench.py --full --steps 300 --warmup 50 --no-vecenv --no-cpu-baseline > $out/bench300.json 2>/dev/null
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-vecenv --no-cpu-baseline > $out/bench20.json 2>/dev/null
 python - <<PY
 import json
 for f in ("bench300","bench20"):

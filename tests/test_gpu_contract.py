@@ -39,7 +39,7 @@ def test_abi_refuses_misuse_loudly():
 
 def test_bench_emits_the_contract_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
-                          "--envs-per-gpu", "256", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                          "--envs-per-gpu", "256", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -51,6 +51,34 @@ def test_bench_emits_the_contract_line():
     assert d["unit"] == "env-steps/s" and d["value"] > 0 and "workload" in d["config"]
     r = d["roofline"]
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
+
+
+def test_plain_bench_run_and_its_output_dump(tmp_path):
+    """Without --full the line holds the headline figure only; --steps sets the timed steps (the dumped ep_steps count them);
+    --dump-outputs writes the last step's outputs as float32 / float64, identical in two runs with the same arguments."""
+    dumps = []
+    for run in range(2):
+        d_out = str(tmp_path / str(run))
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--envs-per-gpu", "256",
+                              "--workload", "maze8192_depth", "--dump-outputs", d_out], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"]
+        assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] * 1e-3 - 256) < 1e-6
+        assert not {"roofline", "kernel_ms", "vecenv", "cpu_baseline", "multi_gpu"} & set(d), sorted(d)
+        names = sorted(os.listdir(d_out))
+        assert names == sorted(n + ".npy" for n in ("obs", "depth", "reward", "done", "ep_steps", "feature", "goal_pos", "sample_env_index"))
+        assert sum(os.path.getsize(os.path.join(d_out, n)) for n in names) <= 64 * 10 ** 6
+        a = {n[:-4]: np.load(os.path.join(d_out, n)) for n in names}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        assert a["obs"].shape == (256, 60, 80, 3) and a["depth"].shape == (256, 60, 80, 1) and a["reward"].shape == (256,)
+        assert np.array_equal(a["sample_env_index"], np.arange(256)) and a["obs"].max() > 0
+        assert a["ep_steps"].max() == 3 + 1
+        dumps.append(a)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_graph_capture_of_a_step():
@@ -232,7 +260,7 @@ def test_shard_exchange_single_gpu_self_test():
     g.drain()
     b.close()
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--envs-per-gpu", "256",
-                          "--no-cpu-baseline", "--no-vecenv", "--force-gather"], capture_output=True, text=True, timeout=600)
+                          "--no-cpu-baseline", "--no-vecenv", "--force-gather", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.strip().splitlines() if l.startswith("{")][0])
     assert "exchange" in d["config"]["parallelism"] and d["value"] > 0
@@ -240,7 +268,7 @@ def test_shard_exchange_single_gpu_self_test():
 
 def test_vecenv_leg_of_the_bench_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--envs-per-gpu", "512",
-                          "--no-cpu-baseline", "--workload", "tmaze_features8192"], capture_output=True, text=True, timeout=600)
+                          "--no-cpu-baseline", "--workload", "tmaze_features8192", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.strip().splitlines() if l.startswith("{")][0])
     v = d["vecenv"]
