@@ -310,7 +310,8 @@ class BatchedMiniWorld:
 
     def render_top_view(self, width=None, height=None):
         """MiniWorldEnv.render_top_view(frame_buffer) for every env (miniworld.py:1087-1158): uint8 [N, height, width, 3] on
-        the device, default the observation size (the reference's default frame buffer is obs_fb)."""
+        the device, default the observation size (the reference's default frame buffer is obs_fb).  Every task: the entity tasks'
+        view draws the current entity list - box tops, the up-facing triangles of meshes, the frames' top strips."""
         W, H = int(width or self.W), int(height or self.H)
         out = self.torch.empty((self.num_envs, H, W, 3), dtype=self.torch.uint8, device=self.device)
         _lib.check(self.L.mwb_render_top_view(self.h, out.data_ptr(), W, H, self._stream()))

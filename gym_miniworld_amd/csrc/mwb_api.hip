@@ -757,10 +757,21 @@ extern "C" int mwb_render(mwb_handle *h, void *stream) {
 extern "C" int mwb_render_top_view(mwb_handle *h, uint8_t *out_dev, int width, int height, void *stream) {
     if (!h || !out_dev) return set_err(MWB_EINVAL, "mwb_render_top_view: null argument");
     if (width < 1 || height < 1 || width > 4096 || height > 4096) return set_err(MWB_EINVAL, "mwb_render_top_view: bad frame size");
-    if (h->dev.ent_task) return set_err(MWB_EINVAL, "mwb_render_top_view: not available for the tasks with mesh entities");
     USE_DEVICE(h->cfg.device);
     int rc = ensure_ready(h, false); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    if (h->dev.ent_task) {   // the current entity list (step_pass 0, as mwb_render), prepared into the view's own frame constants:
+        // the observation's are left as they are, so no later observation, reward or done depends on this call
+        if (!h->view_frame) {
+            rc = dev_alloc(h, &h->view_frame, (size_t)h->dev.N * h->dev.frame_words); if (rc) return rc;
+        }
+        MwbDev v = h->dev;
+        v.frame = h->view_frame; v.stk = nullptr; v.step_pass = 0; v.wg_ts = nullptr;
+        mwb_launch_prep(v, 0, s);
+        rc = check_launch("prep_kernel"); if (rc) return rc;
+        mwb_launch_top_view_ents(v, out_dev, width, height, s);
+        return check_launch("top_view_ents_kernel");
+    }
     mwb_launch_prep(h->dev, 0, s);   // the state may have been set from outside since the last render
     rc = check_launch("prep_kernel"); if (rc) return rc;
     mwb_launch_top_view(h->dev, out_dev, width, height, s);

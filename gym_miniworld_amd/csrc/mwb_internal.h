@@ -231,6 +231,7 @@ void mwb_launch_intersect(const MwbDev &d, int env, int ent, double x, double z,
 void mwb_launch_visible(const MwbDev &d, uint32_t *mask_out, hipStream_t s);   // get_visible_ents for every env
 int mwb_launch_render_view(const MwbDev &d, hipStream_t s);   // the agent's view at d.W x d.H in tiles; 0 ok, -1 LDS, -2 HIP
 void mwb_launch_top_view(const MwbDev &d, uint8_t *out, int W, int H, hipStream_t s);   // render_top_view for every env, [N][H][W][3]
+void mwb_launch_top_view_ents(const MwbDev &d, uint8_t *out, int W, int H, hipStream_t s);   // the same for the entity tasks (tiles)
 int mwb_prepare_kernels(const MwbDev &d);   // 0 ok, -1 world too large for LDS, -2 HIP error, -3 frame too large for the pixel queue
 size_t mwb_reset_lds_bytes(const MwbDev &d);
 size_t mwb_render_lds_bytes(const MwbDev &d);

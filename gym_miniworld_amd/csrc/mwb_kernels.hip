@@ -4115,6 +4115,266 @@ void mwb_launch_top_view(const MwbDev &d, uint8_t *out, int W, int H, hipStream_
     else top_view_kernel<false><<<dim3(d.N), dim3(256), 0, s>>>(d, out, W, H);
 }
 
+// ---- the same view for the entity tasks ("top view of the entity tasks").  Draw order of _render_world: the display
+// list (rooms, then the static entities in list order), the other entities in list order, the agent.  Seen from straight above:
+// a floor, a box's top face, a mesh's up-facing triangles (the obs path's Moeller-Trumbore with a vertical ray in the mesh's frame),
+// the black top strip of an image / text frame (y = pos.y + height / 2, [0, depth] x [-w/2, w/2] in the frame's axes), the agent's
+// triangle; the highest wins, a tie goes to what was drawn first.  Reads only the camera-independent frame constants.  One
+// workgroup per (env, 16 x 16 tile): an 800 x 600 view spreads over the chip, a mesh walk stays on a few CUs.
+#define TOPE_TILE 16
+// nearest front-facing triangle of a mesh along the straight-down ray from lo (mesh frame, mesh units): ray parameter and original
+// index.  The threading of the sign pattern (+x, -y, +z) - only y is negative - visits the higher child first.
+__device__ __forceinline__ bool top_mesh_walk(const float4 *__restrict__ gd, const MwbMeshDesc &md, const float *lo, float &t_best, int &best) {
+    const float ld[3] = {0.0f, -1.0f, 0.0f};
+    const int n_nodes = md.n_nodes;
+    const float4 *nodes = gd + md.node_off + (size_t)(md.n_orders == 8 ? 2u : 0u) * 2u * (uint32_t)n_nodes, *tris = gd + md.tri_off;
+    t_best = INFINITY;
+    best = -1;
+    int node = 0;
+    while (node < n_nodes) {
+        const float4 a = nodes[2 * node], b = nodes[2 * node + 1];
+        const uint32_t fcnt = (uint32_t)__float_as_int(b.w);
+        const int cnt = (int)(fcnt >> 24);
+        // the vertical ray meets the (padded) node box iff the point lies in its xz rectangle; skipped when its top is below the best hit
+        const bool hit = lo[0] >= a.x && lo[0] <= b.x && lo[2] >= a.z && lo[2] <= b.z && lo[1] - b.y <= t_best;
+        if (hit && cnt == 0) { node++; continue; }
+        if (hit) {
+            const int first = (int)(fcnt & 0xFFFFFFu);
+            for (int q = 0; q < cnt; q++) {
+                const float4 *r = tris + 3 * (first + q);
+                float t, u, v, det;
+                if (mesh_tri(lo, ld, r[0], r[1], r[2], true, t, u, v, det)) {
+                    const int idx = __float_as_int(r[2].y);
+                    if (t < t_best || (t == t_best && idx < best)) { t_best = t; best = idx; }   // a tie: the triangle drawn first
+                }
+            }
+        }
+        node = __float_as_int(a.w);   // on past this subtree / leaf
+    }
+    return best >= 0;
+}
+// the sample point (x, z) in a mesh's frame: the obs path's rotation and 1 / scale; y = the ray's origin above the mesh
+__device__ __forceinline__ void top_mesh_point(const float *blk, float x, float z, float *lo) {
+    const float c = blk[FC_BOX_C], s = blk[FC_BOX_S], inv_s = blk[FC_LIT_BOX + FE_MESH_INVS];
+    const float rx = x - blk[FC_BOX_POS], rz = z - blk[FC_BOX_POS + 2];
+    lo[0] = fmaf(rx, c, -(rz * s)) * inv_s; lo[1] = blk[FC_BOX_SY] + 1.0f; lo[2] = fmaf(rx, s, rz * c) * inv_s;
+}
+// shade_mesh_s for the orthographic view: Gouraud colours at the pixel centre (a front-facing triangle faces every ray of the view,
+// so the centre's barycentrics always exist), the +1 pixel neighbours as shifted ray origins for the LOD
+__device__ __noinline__ static void shade_top_mesh(const float *fc, const MwbMeshDesc *mesh_desc, const float4 *mesh_data, const TexLds *tex,
+                                                   const uint32_t *texels, uint32_t key, float xc, float zc, float XS, float ZS, float *col) {
+    const int bi = (int)((key >> 3) & 31u), tri = (int)(key >> 8);
+    const float *blk = fc + bi * FC_BOX_STRIDE;
+    const float *me = blk + FC_LIT_BOX;
+    const MwbMeshDesc &md = mesh_desc[__float_as_int(me[FE_MESH_GEOM])];
+    const float4 *rec = mesh_data + md.tri2_off + 3 * tri, *sh = mesh_data + md.shade_off + 4 * tri;
+    const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], s0 = sh[0], s1 = sh[1], s2 = sh[2], s3 = sh[3];
+    const float nrm[3][3] = {{s0.x, s0.y, s0.z}, {s0.w, s1.x, s1.y}, {s1.z, s1.w, s2.x}};
+    const float tc[6] = {s2.y, s2.z, s2.w, s3.x, s3.y, s3.z};
+    float vc[3][3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float ndl = nrm[k][0] * me[FE_MESH_LL] + nrm[k][1] * me[FE_MESH_LL + 1] + nrm[k][2] * me[FE_MESH_LL + 2];
+        ndl = ndl < 0.0f ? 0.0f : ndl;
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            const float v = me[FE_MESH_AMB + q] + ndl * me[FE_MESH_DIF + q] * me[FE_MESH_KD + q];
+            vc[k][q] = v > 1.0f ? 1.0f : v;
+        }
+    }
+    const float ld[3] = {0.0f, -1.0f, 0.0f};
+    float lo[3], t, u, v, det;
+    top_mesh_point(blk, xc, zc, lo);
+    mesh_tri(lo, ld, r0, r1, r2, false, t, u, v, det);
+    const float ub = u / det, vb = v / det;
+#pragma unroll
+    for (int q = 0; q < 3; q++) col[q] = fmaf(vb, vc[2][q] - vc[0][q], fmaf(ub, vc[1][q] - vc[0][q], vc[0][q]));
+    const int tex_id = __float_as_int(me[FE_MESH_TEX]);
+    if (tex_id >= 0) {
+        const float s_0 = fmaf(vb, tc[4] - tc[0], fmaf(ub, tc[2] - tc[0], tc[0])), t_0 = fmaf(vb, tc[5] - tc[1], fmaf(ub, tc[3] - tc[1], tc[1]));
+        float l1[3], l2[3], u1, v1, d1, u2, v2, d2;
+        top_mesh_point(blk, xc + XS, zc, l1);
+        top_mesh_point(blk, xc, zc - ZS, l2);
+        mesh_tri(l1, ld, r0, r1, r2, false, t, u1, v1, d1);
+        mesh_tri(l2, ld, r0, r1, r2, false, t, u2, v2, d2);
+        u1 /= d1; v1 /= d1; u2 /= d2; v2 /= d2;
+        const float s_1 = fmaf(v1, tc[4] - tc[0], fmaf(u1, tc[2] - tc[0], tc[0])), t_1 = fmaf(v1, tc[5] - tc[1], fmaf(u1, tc[3] - tc[1], tc[1]));
+        const float s_2 = fmaf(v2, tc[4] - tc[0], fmaf(u2, tc[2] - tc[0], tc[0])), t_2 = fmaf(v2, tc[5] - tc[1], fmaf(u2, tc[3] - tc[1], tc[1]));
+        float texel[3];
+        sample_texture(texels, tex[tex_id], s_0, t_0, s_1, t_1, s_2, t_2, true, texel);
+#pragma unroll
+        for (int q = 0; q < 3; q++) col[q] = col[q] * (texel[q] * (1.0f / 255.0f));
+    }
+}
+__global__ void __launch_bounds__(256) top_view_ents_kernel(MwbDev d, uint8_t *__restrict__ out, int W, int H, int tiles_x, int tiles) {
+    __shared__ TexLds tex[MWB_MAX_TEX];
+    __shared__ int draw_s[MWB_MAX_ENTS];
+    __shared__ int n_draw_s;
+    __shared__ float agent_red_s;
+    const int e = blockIdx.x / tiles, tile = blockIdx.x - e * tiles, tid = threadIdx.x;
+    for (int i = tid; i < (int)(sizeof(TexLds) / 4) * d.n_tex; i += 256) ((uint32_t *)tex)[i] = ((const uint32_t *)d.tex_desc)[i];
+    int n_rooms = d.n_rrooms[e];
+    if (n_rooms < 0) n_rooms = 0;
+    const float *rooms = d.rooms + (size_t)e * d.R_max * d.room_words;
+    const float *fc = d.frame + (size_t)e * d.frame_words;
+    if (tid == 0) {
+        // the entity slots in draw order: static ones (compiled into the display list, miniworld.py:1047-1052), then the others
+        // (miniworld.py:1070-1074), each in list order; the agent is drawn last
+        const uint8_t *ord = d.ent_order + (size_t)e * MWB_ORDER_STRIDE;
+        const int n_ord = d.n_order[e] < MWB_MAX_ENTS + 1 ? d.n_order[e] : MWB_MAX_ENTS + 1;
+        int n = 0;
+        bool flat = false;   // a Box or a frame in the list: its last glNormal3f is (0, -1, 0)
+        for (int pass = 1; pass >= 0; pass--)
+            for (int q = 0; q < n_ord; q++) {
+                const int sl = ord[q];
+                if (sl == MWB_ENT_AGENT || sl >= d.n_boxes || n >= MWB_MAX_ENTS) continue;
+                const int meta = d.ent_meta[(size_t)sl * d.N + e];
+                if (MWB_META_STATIC(meta) != pass) continue;
+                draw_s[n++] = sl;
+                flat = flat || MWB_META_KIND(meta) != MWB_ENT_MESH;
+            }
+        n_draw_s = n;
+        // The agent's triangle issues no glNormal3f (entity.py:494-514): it is lit with the last one issued before it, a mesh's vertex
+        // arrays changing nothing (frozen).  Without a box or a frame that is the last wall quad of the display list's
+        // rooms: the inward normal of the last side of the last room that still has a wall piece (sides in outline order).
+        int side = 3;
+        if (!flat && n_rooms > 0) {
+            const float *r = rooms + (n_rooms - 1) * MWB_ROOM_WORDS;
+            for (; side > 0; side--) {
+                const uint32_t nbr = ((uint32_t)__float_as_int(r[RW_NBR01 + (side >> 1)]) >> ((side & 1) * 16)) & 0xFFFFu;
+                if (nbr == RW_NO_NBR) break;
+                const float *sd = r + RW_SIDE0 + RW_SIDE_WORDS * side;
+                const float lo_ = (side & 1) ? r[RW_MINX] : r[RW_MINZ], hi_ = (side & 1) ? r[RW_MAXX] : r[RW_MAXZ];
+                if (sd[RS_LO] > lo_ || sd[RS_HI] < hi_ || sd[RS_MAXY] < r[RW_HEIGHT]) break;   // the opening leaves a wall piece
+            }
+        }
+        agent_red_s = flat ? fc[FC_LIT_CEIL] : fc[FC_LIT_WALL + 3 * side];   // red * the lit white of that normal
+    }
+    __syncthreads();
+    const int tile_y = tile / tiles_x, tile_x = tile - tile_y * tiles_x;
+    const int px = tile_x * TOPE_TILE + (tid & (TOPE_TILE - 1)), py = tile_y * TOPE_TILE + tid / TOPE_TILE;
+    if (px >= W || py >= H) return;
+    const int n_draw = n_draw_s;
+    double min_x = d.world_ext[e * 4 + 0] - 1, max_x = d.world_ext[e * 4 + 1] + 1, min_z = d.world_ext[e * 4 + 2] - 1, max_z = d.world_ext[e * 4 + 3] + 1;
+    {
+        const double width = max_x - min_x, height = max_z - min_z, aspect = width / height, fb_aspect = (double)W / (double)H;
+        if (aspect > fb_aspect) { const double new_h = width / fb_aspect, h_diff = new_h - height; min_z -= h_diff / 2; max_z += h_diff / 2; }
+        else if (aspect < fb_aspect) { const double new_w = height * fb_aspect, w_diff = new_w - width; min_x -= w_diff / 2; max_x += w_diff / 2; }
+    }
+    const float X0 = (float)min_x, XS = (float)((max_x - min_x) / (double)W), Z1 = (float)max_z, ZS = (float)((max_z - min_z) / (double)H);
+    float tri[3][2];
+    {
+        const double adir = d.agent_dir[e], ar = d.agent_radius, ax = d.agent_x[e], az = d.agent_z[e];
+        const double c = ref_cos(adir), s_ = ref_sin(adir);
+        const double dvx = c * ar, dvz = -s_ * ar, rvx = s_ * ar, rvz = c * ar;
+        tri[0][0] = (float)(ax + dvx); tri[0][1] = (float)(az + dvz);
+        tri[1][0] = (float)(ax + 0.75 * (rvx - dvx)); tri[1][1] = (float)(az + 0.75 * (rvz - dvz));
+        tri[2][0] = (float)(ax + 0.75 * (-rvx - dvx)); tri[2][1] = (float)(az + 0.75 * (-rvz - dvz));
+    }
+    const float agent_y = (float)(0.0 + 1.6);   // pos.y + Agent.height (entity.py:449)
+    enum { T_SKY = 0, T_FLOOR = 1, T_BOX = 4, T_AGENT = 5, T_MESH = 6, T_FRAME = 7 };
+    auto classify = [&](float x, float z) -> uint32_t {
+        uint32_t key = T_SKY;
+        float ybest = -INFINITY;
+        for (int i = 0; i < n_rooms; i++) {   // rectangle rooms: the floor of the first room holding the point; ceilings face down
+            const float4 rect = *(const float4 *)(rooms + i * MWB_ROOM_WORDS + RW_MINX);
+            if (x >= rect.x && x <= rect.y && z >= rect.z && z <= rect.w) { key = T_FLOOR | ((uint32_t)i << 3); ybest = 0.0f; break; }
+        }
+        for (int q = 0; q < n_draw; q++) {
+            const int bi = draw_s[q];
+            const float *blk = fc + bi * FC_BOX_STRIDE;
+            const float kind = blk[FC_BOX_HX];
+            const float rx = x - blk[FC_BOX_POS], rz = z - blk[FC_BOX_POS + 2];
+            if (kind >= 0.0f) {   // a box: its top face
+                const float lx = rx * blk[FC_BOX_C] - rz * blk[FC_BOX_S], lz = rx * blk[FC_BOX_S] + rz * blk[FC_BOX_C];
+                const float top = blk[FC_BOX_POS + 1] + blk[FC_BOX_SY];
+                if (fabsf(lx) <= kind && fabsf(lz) <= blk[FC_BOX_HZ] && top > ybest) { key = T_BOX | ((uint32_t)bi << 3); ybest = top; }
+            } else if (kind == -2.0f) {   // an image / text frame: the black top strip
+                const float *fe = blk + FC_LIT_BOX;
+                const float top = blk[FC_BOX_POS + 1] + fe[FE_FRAME_HY];
+                if (top > ybest) {
+                    // its corners moved into the world (glTranslatef + glRotatef of the Top quad's vertices), then inclusive edge tests
+                    // as for the agent: a frame on a wall has its edge exactly on the wall, where the sample grid may fall
+                    const float c = blk[FC_BOX_C], s = blk[FC_BOX_S], sx = fe[FE_FRAME_SX], hz = fe[FE_FRAME_HZ];
+                    const float lq[4][2] = {{sx, hz}, {sx, -hz}, {0.0f, -hz}, {0.0f, hz}};
+                    float qx[4], qz[4];
+#pragma unroll
+                    for (int k = 0; k < 4; k++) { qx[k] = blk[FC_BOX_POS] + (c * lq[k][0] + s * lq[k][1]); qz[k] = blk[FC_BOX_POS + 2] + (c * lq[k][1] - s * lq[k][0]); }
+                    bool all_pos = true, all_neg = true;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const int k1 = (k + 1) & 3;
+                        const float sg = fmaf(qx[k1] - qx[k], z - qz[k], -((qz[k1] - qz[k]) * (x - qx[k])));
+                        all_pos = all_pos && sg >= 0.0f; all_neg = all_neg && sg <= 0.0f;
+                    }
+                    if (all_pos || all_neg) { key = T_FRAME | ((uint32_t)bi << 3); ybest = top; }
+                }
+            } else if (kind == -1.0f) {   // a mesh: its highest up-facing triangle
+                const float *me = blk + FC_LIT_BOX;
+                float lo[3];
+                top_mesh_point(blk, x, z, lo);
+                if (!(fabsf(lo[0]) <= me[FE_MESH_BHX] && fabsf(lo[2]) <= me[FE_MESH_BHZ])) continue;
+                float t;
+                int idx;
+                if (!top_mesh_walk(d.mesh_data, d.mesh_desc[__float_as_int(me[FE_MESH_GEOM])], lo, t, idx)) continue;
+                const float y = fmaf(lo[1] - t, 1.0f / me[FE_MESH_INVS], blk[FC_BOX_POS + 1]);   // the hit's height in the world
+                if (y > ybest) { key = T_MESH | ((uint32_t)bi << 3) | ((uint32_t)idx << 8); ybest = y; }
+            }
+        }
+        {
+            float sgn[3];
+#pragma unroll
+            for (int q = 0; q < 3; q++) {
+                const float *a = tri[q], *b = tri[(q + 1) % 3];
+                sgn[q] = fmaf(b[0] - a[0], z - a[1], -((b[1] - a[1]) * (x - a[0])));
+            }
+            const bool in = (sgn[0] >= 0 && sgn[1] >= 0 && sgn[2] >= 0) || (sgn[0] <= 0 && sgn[1] <= 0 && sgn[2] <= 0);
+            if (in && agent_y > ybest) key = T_AGENT;
+        }
+        return key;
+    };
+    const float cx = (float)px + 0.5f, cy = (float)(H - 1 - py) + 0.5f;
+    uint32_t keys[8];
+#pragma unroll 1
+    for (int k = 0; k < 8; k++) keys[k] = classify(fmaf(cx + c_sample_x[k], XS, X0), fmaf(-(cy + c_sample_y[k]), ZS, Z1));
+    const float xc = fmaf(cx, XS, X0), zc = fmaf(-cy, ZS, Z1);
+    float acc[3] = {0, 0, 0};
+    uint32_t done_mask = 0;
+#pragma unroll 1
+    for (int k = 0; k < 8; k++) {
+        if (done_mask & (1u << k)) continue;
+        int cnt = 0;
+        for (int j = k; j < 8; j++)
+            if (!(done_mask & (1u << j)) && keys[j] == keys[k]) { cnt++; done_mask |= 1u << j; }
+        const uint32_t kind = keys[k] & 7u, idx = (keys[k] >> 3) & 31u;
+        float col[3];
+        if (kind == T_SKY) { col[0] = fc[FC_SKY]; col[1] = fc[FC_SKY + 1]; col[2] = fc[FC_SKY + 2]; }
+        else if (kind == T_BOX) { const float *lb = fc + idx * FC_BOX_STRIDE + FC_LIT_BOX + 3 * 3; col[0] = lb[0]; col[1] = lb[1]; col[2] = lb[2]; }   // face 3 = +y
+        else if (kind == T_FRAME) { col[0] = 0.0f; col[1] = 0.0f; col[2] = 0.0f; }   // glColor3f(0, 0, 0): black whatever the light
+        else if (kind == T_AGENT) { col[0] = agent_red_s; col[1] = 0.0f; col[2] = 0.0f; }
+        else if (kind == T_MESH) shade_top_mesh(fc, d.mesh_desc, d.mesh_data, tex, d.texels, keys[k], xc, zc, XS, ZS, col);
+        else {
+            const uint32_t room = keys[k] >> 3;
+            const uint32_t texw = (uint32_t)__float_as_int(rooms[room * MWB_ROOM_WORDS + RW_TEX]);
+            const TexLds &T = tex[(texw >> 8) & 255u];
+            float texel[3];
+            sample_texture(d.texels, T, xc * T.sc_s, zc * T.sc_t, (xc + XS) * T.sc_s, zc * T.sc_t, xc * T.sc_s, (zc - ZS) * T.sc_t, true, texel);
+            for (int q = 0; q < 3; q++) col[q] = fc[FC_LIT_FLOOR + q] * (texel[q] * (1.0f / 255.0f));
+        }
+        for (int q = 0; q < 3; q++) acc[q] += (float)cnt * col[q];
+    }
+    uint8_t *o = out + ((size_t)e * W * H + (size_t)py * W + px) * 3;
+    for (int q = 0; q < 3; q++) {
+        float v = acc[q] * 0.125f;
+        v = __builtin_amdgcn_fmed3f(v, 0.0f, 1.0f);
+        o[q] = (uint8_t)(unsigned)(v * 255.0f + 0.5f);
+    }
+}
+void mwb_launch_top_view_ents(const MwbDev &d, uint8_t *out, int W, int H, hipStream_t s) {
+    const int tiles_x = (W + TOPE_TILE - 1) / TOPE_TILE, tiles = tiles_x * ((H + TOPE_TILE - 1) / TOPE_TILE);
+    top_view_ents_kernel<<<dim3((unsigned)(tiles * d.N)), dim3(256), 0, s>>>(d, out, W, H, tiles_x, tiles);
+}
+
 // =========================================================================== get_visible_ents
 // MiniWorldEnv.get_visible_ents (miniworld.py:1222-1315) for the whole batch: rooms into the observation frame (8 samples, the
 // camera of render_obs), then per entity but the agent, in list order, an axis-aligned 0.2 m cube at its position inside a

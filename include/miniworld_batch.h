@@ -324,7 +324,15 @@ int mwb_get_geometry(mwb_handle *h, int env, float *rooms, int max_rooms, double
 /* replaces: MiniWorldEnv.render_top_view(frame_buffer) (miniworld.py:1087-1158; `render(view='top')` 1317-1335) for the whole
  * batch: the floorplan from straight above, extents + 1 m widened to the frame's aspect, floors, box tops and the agent's
  * triangle.  out_dev: uint8 [N][height][width][3] in device memory, any frame size; enqueued on `stream`.  A display /
- * debugging view, not part of the step pipeline. */
+ * debugging view, not part of the step pipeline.
+ * Entity tasks (MWB_TASK_PICKUPOBJS and later): the CURRENT entity list (as mwb_render draws it: an entity that left the list is not
+ * drawn, a carried one is at its carry pose) in the reference's draw order - rooms, static entities, the others in list order, the
+ * agent - the highest up-facing surface winning: box tops, the up-facing triangles of meshes (Gouraud-shaded, textured ones
+ * modulated), the black top strip of image / text frames.  The agent's triangle is lit with the normal of the last glNormal3f issued
+ * before it, vertex arrays changing nothing: (0, -1, 0) if the list holds a box or a frame, else the inward normal of the last wall
+ * side of the last room (frozen).  Pinned to the reference's captured map-view streams within +-1 at >= 99.5 %
+ * of the pixels (tests/test_gpu_top_view_ents.py); the agent's shade in the meshes-only case is parity unpinned against real
+ * OpenGL.  Changes no later observation, reward or done. */
 int mwb_render_top_view(mwb_handle *h, uint8_t *out_dev, int width, int height, void *stream);
 
 /* replaces: MiniWorldEnv.render_obs(frame_buffer) / render_depth(frame_buffer) with ANOTHER frame buffer than the observation's
