@@ -40,20 +40,19 @@ def test_vecenv_matches_per_env_oracle_with_autoreset(oracle_mod):
 
 @pytest.mark.parametrize("env_id", ["MiniWorld-OneRoomS6-v0", "MiniWorld-CollectHealth-v0", "MiniWorld-PickupObjs-v0"])
 def test_frame_stack_semantics(env_id):
-    """VecPyTorchFrameStack (envs.py:135-165) restated in numpy on the same observation stream (the fused window: also the entity
-    tasks' render kernel writes it)."""
+    """VecPyTorchFrameStack (envs.py:135-165) restated (tests/stack_ref.py) on the same observation stream (the fused window: also
+    the entity tasks' render kernel writes it)."""
     import torch
     from gym_miniworld_amd.vec_env import MiniWorldVecEnv
+    from stack_ref import FrameStackRef
     n = 5
     kw = {"max_episode_steps": 40} if "PickupObjs" in env_id else {}
     v = MiniWorldVecEnv(env_id, n, seed=3, frame_stack=4, **kw)
     plain = MiniWorldVecEnv(env_id, n, seed=3, frame_stack=0, **kw)
     assert v.observation_space.shape == (12, 80, 60)
-    st = v.reset().cpu().numpy()
-    ob = plain.reset().cpu().numpy()
-    ref = np.zeros((n, 12, 80, 60), np.float32)
-    ref[:, -3:] = ob
-    assert np.array_equal(st, ref)
+    ref = FrameStackRef(n, 4, (3, 80, 60), dtype=torch.float32)
+    st = v.reset().cpu()
+    assert st.dtype == torch.float32 and torch.equal(st, ref.reset(plain.reset().cpu()))
     g = torch.Generator().manual_seed(1)
     any_done = False
     for t in range(130):
@@ -61,11 +60,8 @@ def test_frame_stack_semantics(env_id):
         st, _, done, _ = v.step(a)
         ob, _, done2, _ = plain.step(a)
         assert np.array_equal(done, done2)
-        ref[:, :-3] = ref[:, 3:].copy()
-        ref[done] = 0
-        ref[:, -3:] = ob.cpu().numpy()
         any_done |= bool(done.any())
-        assert np.array_equal(st.cpu().numpy(), ref)
+        assert torch.equal(st.cpu(), ref.step(ob.cpu(), done))
     assert any_done
     v.close(); plain.close()
 
