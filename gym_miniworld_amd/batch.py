@@ -476,6 +476,14 @@ class BatchedMiniWorld:
             self.stack = self._stack_base[:, first.value:first.value + self._stack_c]
         return self.stack
 
+    def frame_reuse_stats(self):
+        """(frames reused, frames rendered) by the step passes since the last call (mwb_frame_reuse_stats; synchronous).  A step
+        that leaves an env as it was - a move a wall blocks - copies the env's last frame from a private cache instead of
+        rendering it; MWB_NO_FRAME_REUSE=1 in the environment when the batch is created turns that off."""
+        out = (ctypes.c_ulonglong * 2)()
+        _lib.check(self.L.mwb_frame_reuse_stats(self.h, out))
+        return int(out[0]), int(out[1])
+
     def timing_enable(self, on=True):
         """on: False / True, or an int n > 1 to time every n-th pass only (the events cost ~20 us per pass)."""
         _lib.check(self.L.mwb_timing_enable(self.h, int(on)))

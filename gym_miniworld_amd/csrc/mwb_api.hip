@@ -76,6 +76,7 @@ struct mwb_handle {
     float4 *mesh_data_dev;
     MwbMeshDesc *mesh_desc_dev;
     float *view_frame;   // frame constants of mwb_render_view's size (lazily allocated)
+    bool frame_reuse;    // the last-frame cache exists and step passes copy from it (off: MWB_NO_FRAME_REUSE=1, or frames rendered in tiles)
 };
 
 extern "C" const char *mwb_last_error(void) { return g_err.c_str(); }
@@ -391,6 +392,16 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
             d.tile_w = tw < d.W ? tw : d.W; d.tile_h = th < d.H ? th : d.H;
         }
     }
+    // last-frame reuse: N x (W*H*3 [+ W*H*4 with depth]) bytes of cache and two flags per env; MWB_NO_FRAME_REUSE=1 turns it off
+    { const char *no = getenv("MWB_NO_FRAME_REUSE"); h->frame_reuse = !(no && atoi(no)) && d.tile_w == 0; }
+    rc = dev_alloc(h, &d.reuse_stats, (size_t)2);
+    if (rc == MWB_OK && h->frame_reuse) {
+        rc = dev_alloc(h, &d.frame_cache, N * d.W * d.H * 3);
+        if (rc == MWB_OK && d.want_depth) rc = dev_alloc(h, &d.depth_cache, N * d.W * d.H);
+        if (rc == MWB_OK) rc = dev_alloc(h, &d.frame_cached, N);
+        if (rc == MWB_OK) rc = dev_alloc(h, &d.frame_same, N);
+    }
+    if (rc != MWB_OK) { mwb_destroy(h); return rc; }
     if (int prc = mwb_prepare_kernels(d)) {
         mwb_destroy(h);
         return set_err(prc == -2 ? MWB_EHIP : MWB_EINVAL,
@@ -597,6 +608,15 @@ static int upload_meshes(mwb_handle *h) {   // the caller holds the device guard
 }
 
 // ---------------------------------------------------------------------------------- simulation
+// Something the frames of envs [first, first + count) depend on has been changed from outside without a render: their cached
+// frames no longer show their state.  The callers have synchronised the device and hold the device guard.
+static int invalidate_frames(mwb_handle *h, int first, int count) {
+    if (!h->dev.frame_cached || count <= 0) return MWB_OK;
+    HIP_TRY(hipMemset(h->dev.frame_cached + first, 0, (size_t)count));
+    HIP_TRY(hipDeviceSynchronize());
+    return MWB_OK;
+}
+
 extern "C" int mwb_seed(mwb_handle *h, const uint64_t *seeds) {
     if (!h || !seeds) return set_err(MWB_EINVAL, "mwb_seed: null argument");
     USE_DEVICE(h->cfg.device);
@@ -609,7 +629,7 @@ extern "C" int mwb_seed(mwb_handle *h, const uint64_t *seeds) {
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h->dev.rng, st.data(), st.size() * 4, hipMemcpyHostToDevice));
     h->seeded = true;
-    return MWB_OK;
+    return invalidate_frames(h, 0, h->dev.N);
 }
 
 static int check_launch(const char *what) {
@@ -663,8 +683,8 @@ static int stack_advance(mwb_handle *h, int after_reset, hipStream_t s) {
 
 static int ensure_ready(mwb_handle *h, bool renders = true) {   // the caller holds the device guard
     if (!h->seeded) return set_err(MWB_ESTATE, "mwb_seed must be called before reset/step (the reference seeds from entropy; this library refuses to)");
-    if (h->textures_dirty || !h->have_textures) { int rc = upload_textures(h); if (rc) return rc; }
-    if (h->dev.ent_task && (h->meshes_dirty || !h->mesh_data_dev)) { int rc = upload_meshes(h); if (rc) return rc; }
+    if (h->textures_dirty || !h->have_textures) { int rc = upload_textures(h); if (rc) return rc; rc = invalidate_frames(h, 0, h->dev.N); if (rc) return rc; }
+    if (h->dev.ent_task && (h->meshes_dirty || !h->mesh_data_dev)) { int rc = upload_meshes(h); if (rc) return rc; rc = invalidate_frames(h, 0, h->dev.N); if (rc) return rc; }
     if (renders) h->have_obs = true;
     return MWB_OK;
 }
@@ -674,7 +694,7 @@ extern "C" int mwb_reset(mwb_handle *h, const uint8_t *mask_dev, void *stream) {
     USE_DEVICE(h->cfg.device);
     int rc = ensure_ready(h); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    h->dev.step_pass = 0;
+    h->dev.step_pass = 0; h->dev.reuse_pass = 0;   // every frame is rendered (and the last-frame cache refreshed)
     rc = timing_begin(h, s); if (rc) return rc;
     rc = stack_advance(h, mask_dev == nullptr, s); if (rc) return rc;   // a full reset restarts the window; a partial one is a step for the others
     mwb_launch_mark_reset(h->dev, mask_dev, s);
@@ -707,6 +727,7 @@ static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *s
     int rc = ensure_ready(h); if (rc) return rc;
     if (!actions_dev) return set_err(MWB_EINVAL, "mwb_step: null actions");
     hipStream_t s = (hipStream_t)stream;
+    h->dev.reuse_pass = 1;   // an env the step kernel finds unchanged gets its last frame copied instead of rendered (d.frame_same)
     h->dev.step_pass = 1;   // the frames of this pass are the step's own (entity tasks: what a task rule removed is still drawn)
     rc = timing_begin(h, s); if (rc) return rc;
     rc = stack_advance(h, 0, s); if (rc) return rc;
@@ -748,6 +769,7 @@ extern "C" int mwb_render(mwb_handle *h, void *stream) {
     USE_DEVICE(h->cfg.device);
     int rc = ensure_ready(h); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    h->dev.reuse_pass = 0;
     h->dev.step_pass = 0;   // the current state (render_obs() called again shows what the task rule left)
     rc = timing_begin(h, s); if (rc) return rc;
     TMARK(1); TMARK(5); TMARK(6); TMARK(2);
@@ -791,6 +813,7 @@ extern "C" int mwb_render_view(mwb_handle *h, uint8_t *out_dev, float *depth_dev
     MwbDev v = h->dev;
     v.W = width; v.H = height; v.layout = MWB_LAYOUT_HWC; v.obs = out_dev; v.depth = depth_dev; v.want_depth = depth_dev ? 1 : 0;
     v.frame = h->view_frame; v.stk = nullptr; v.step_pass = 0; v.wg_ts = nullptr;
+    v.frame_cache = nullptr; v.depth_cache = nullptr; v.frame_cached = nullptr; v.frame_same = nullptr; v.reuse_pass = 0;   // not the observation
     mwb_launch_prep(v, 0, s);
     rc = check_launch("prep_kernel"); if (rc) return rc;
     const int lrc = mwb_launch_render_view(v, s);
@@ -1035,6 +1058,7 @@ extern "C" int mwb_set_state(mwb_handle *h, int first, int count, const mwb_stat
     const size_t N = (size_t)d.N;
     const int B = d.n_boxes;
     int rc;
+    if ((rc = invalidate_frames(h, first, count))) return rc;   // first: an error half-way leaves no stale frame trusted
     if (in->agent_pos) {
         std::vector<double> a(count), b(count);
         for (int i = 0; i < count; i++) { a[i] = in->agent_pos[i * 3]; b[i] = in->agent_pos[i * 3 + 2]; }
@@ -1111,6 +1135,7 @@ extern "C" int mwb_set_agent(mwb_handle *h, int first, int count, const double *
     if (first < 0 || count < 0 || first + count > d.N) return set_err(MWB_EINVAL, "mwb_set_agent: env range out of bounds");
     USE_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize());
+    if (int rc = invalidate_frames(h, first, count)) return rc;
     if (pos_xz) {
         std::vector<double> a(count), b(count);
         for (int i = 0; i < count; i++) { a[i] = pos_xz[i * 2]; b[i] = pos_xz[i * 2 + 1]; }
@@ -1149,13 +1174,24 @@ extern "C" int mwb_debug_counters(mwb_handle *h, unsigned long long *out8, int r
     return MWB_OK;
 }
 
+/* frames the step passes (mwb_step / mwb_step_i64) took from the last-frame cache / rendered since the last call */
+extern "C" int mwb_frame_reuse_stats(mwb_handle *h, unsigned long long out[2]) {
+    if (!h || !out) return set_err(MWB_EINVAL, "mwb_frame_reuse_stats: null argument");
+    USE_DEVICE(h->cfg.device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, h->dev.reuse_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(h->dev.reuse_stats, 0, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipDeviceSynchronize());
+    return MWB_OK;
+}
+
 extern "C" int mwb_set_domain_rand(mwb_handle *h, int domain_rand) {
     if (!h) return set_err(MWB_EINVAL, "mwb_set_domain_rand: null handle");
     USE_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize());   // kernels in flight took the struct by value; order the change after them
     h->dev.domain_rand = domain_rand ? 1 : 0;
     h->cfg.domain_rand = h->dev.domain_rand;
-    return MWB_OK;
+    return invalidate_frames(h, 0, h->dev.N);
 }
 
 extern "C" int mwb_set_task_state(mwb_handle *h, int first, int count, const int64_t *episode_count, const int64_t *task_step_count,
@@ -1165,6 +1201,7 @@ extern "C" int mwb_set_task_state(mwb_handle *h, int first, int count, const int
     if (first < 0 || count < 0 || first + count > d.N) return set_err(MWB_EINVAL, "mwb_set_task_state: env range out of bounds");
     USE_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize());
+    if (int rc = invalidate_frames(h, first, count)) return rc;
     if (episode_count) HIP_TRY(hipMemcpy(d.episode_count + first, episode_count, count * sizeof(int64_t), hipMemcpyHostToDevice));
     if (task_step_count) HIP_TRY(hipMemcpy(d.task_step_count + first, task_step_count, count * sizeof(int64_t), hipMemcpyHostToDevice));
     if (goal_idx) {

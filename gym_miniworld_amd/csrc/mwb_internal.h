@@ -210,6 +210,16 @@ struct MwbDev {
     const float4 *mesh_data;
     MwbMeshDims mesh_dims[MWB_MAX_MESH_DIMS];
     int n_mesh_dims;
+    // ---- last-frame reuse (null / 0 when it is off: MWB_NO_FRAME_REUSE, or frames rendered in tiles).  A step that leaves an env's
+    // pose, entities and episode as they were (a blocked move) would render the frame it rendered the step before: the bulk
+    // pass copies that frame from a private cache instead (the outputs are the caller's to scribble on, so they cannot be it).
+    uint8_t *frame_cache;   // [N][W*H*3] the last frame every env's workgroup(s) produced, in the handle's layout
+    float *depth_cache;     // [N][W*H] its depth map (want_depth)
+    uint8_t *frame_cached;  // [N] frame_cache[e] shows env e's current state: set by render_env's copy-out, cleared by the host's setters
+    uint8_t *frame_same;    // [N] written by the step kernels every step: this step changed nothing env e's frame depends on AND
+                            //     frame_cached[e] was set - the bulk pass of the same step copies instead of rendering
+    int reuse_pass;         // the render launch belongs to a step (honours frame_same); 0: mwb_render / mwb_reset render everything
+    unsigned long long *reuse_stats;   // [2] frames reused / rendered by step passes since mwb_frame_reuse_stats last read them
     int tile_w, tile_h;   // entity tasks: every frame is rendered as tiles of this size, one workgroup each (0: whole frames)
     unsigned long long *dbg_counters;   // [8] or null: walk_meshes counters (MWB_EXP bit 2)
     int exp_flags;   // MWB_EXP env var at mwb_create: bit 0 = meshes are never hit, bit 1 = flat grey mesh shading (timing experiments)

@@ -157,6 +157,7 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
 #pragma unroll
     for (int b = 0; b < NBX; b++) { bx[b] = 0; bz[b] = 0; by[b] = 0; brad[b] = 0; bsz[b] = 0; }
     int carried = -1;   // agent.carrying as a box index
+    bool same = true;   // this step has written nothing the env's frame depends on (d.frame_same; a skipped env stays true)
     const double arad = d.agent_radius;
     if (blockIdx.x == 0 && threadIdx.x == 0 && d.order_state[1]) {   // adopt the dispatch order completed beside the last pass
         d.order_state[0] ^= 1; d.order_state[1] = 0;                  // (nothing reads the maps while step_kernel runs)
@@ -167,6 +168,7 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
             d.reward[e] = -99.0f; d.reward64[e] = -99.0; d.done[e] = 0; d.ep_steps[e] = d.step_count[e];
             d.reset_set[e] = 0;
             d.feature[e * 2] = 0.0f; d.feature[e * 2 + 1] = 0.0f;   // info = {"feature": [0, 0]}
+            if (d.frame_same) d.frame_same[e] = d.frame_cached[e];   // not stepped: the frame on record is the frame
         }
         if (live) {
             a = actions[(size_t)e * d.act_stride];   // stride 2: the low words of an int64 action tensor (mwb_step_i64)
@@ -217,6 +219,7 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
                             const size_t be = (size_t)b * d.N + e;
                             d.box_x[be] = qx; d.box_z[be] = qz;
                             d.box_dir[be] += g.uniform(-3.141592653589793 / 5, 3.141592653589793 / 5);
+                            same = false;
                         }
                     }
                 }
@@ -321,6 +324,7 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
         cx = cx + 0.0 * yp; cz = cz + 0.0 * yp;   // pos + Y_VEC * y_pos
     };
     auto store_carried = [&](double cx, double cy, double cz, bool set_dir) {
+        same = false;
 #pragma unroll
         for (int b = 0; b < NBX; b++)
             if (b == carried) {
@@ -339,7 +343,7 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
             if (intersect_serial(carried, cx, cz, pick(brad, carried), true)) hit = true;
             else store_carried(cx, cy, cz, false);
         }
-        if (!hit) { ax = nx; az = nz; d.agent_x[e] = ax; d.agent_z[e] = az; }
+        if (!hit) { ax = nx; az = nz; d.agent_x[e] = ax; d.agent_z[e] = az; same = false; }
     } else if (a == 0 || a == 1) {   // turn_agent, miniworld.py:635-656
         double ta = (a == 0) ? turn_step : -turn_step;
         ta *= (3.141592653589793 / 180);
@@ -352,17 +356,19 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
             else store_carried(cx, cy, cz, true);
         }
         d.agent_dir[e] = adir;
+        if (__double_as_longlong(adir) != __double_as_longlong(orig)) same = false;
     } else if (a == 4) {   // pickup, miniworld.py:682-689: the first entity within 1.2 r of a point 1.5 r ahead of the agent
         const double c = ref_cos(adir), s_ = ref_sin(adir);
         const double tx = ax + (c * 1.5) * arad, tz = az + ((-s_) * 1.5) * arad;
         const int hit = intersect_serial(NB, tx, tz, 1.2 * arad, true);
-        if (carried < 0 && hit >= 2) carried = hit - 2;   // a Box is not static (entity.py:40-46)
+        if (carried < 0 && hit >= 2) { carried = hit - 2; same = false; }   // a Box is not static (entity.py:40-46)
     } else if (a == 5) {   // drop, miniworld.py:692-695
         if (carried >= 0) {
 #pragma unroll
             for (int b = 0; b < NBX; b++)
                 if (b == carried) { by[b] = 0.0; d.box_y[(size_t)b * d.N + e] = 0.0; }
             carried = -1;
+            same = false;
         }
     }
     if (carried >= 0) {   // miniworld.py:698-701: the carried entity follows the agent
@@ -412,6 +418,8 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
     const bool regen = done && d.auto_reset;   // worker auto-reset, vec_env/subproc_vec_env.py:10-13
     d.reset_set[e] = (uint8_t)regen;
     if (regen) d.reset_list[atomicAdd(d.reset_count, 1)] = e;
+    // the blocked move with nothing carried (and every action that is none) leaves the frame of the step before standing
+    if (d.frame_same) d.frame_same[e] = (uint8_t)(same && !regen && d.frame_cached[e]);
 }
 
 // ---- MiniWorldEnv.step for the tasks with a general entity list (PickupObjs, RoomObjs, CollectHealth, ThreeRooms, Sign, Sidewalk,
@@ -428,6 +436,8 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
     const int E = d.n_boxes;
     if (skip && skip[e]) {   // the fork's 'dummy' command, vec_env/subproc_vec_env.py:26-31
         d.reward[e] = -99.0f; d.reward64[e] = -99.0; d.done[e] = 0; d.ep_steps[e] = d.step_count[e];
+        // not stepped: the frame on record is the frame - unless it still shows the entity an override put back for the step before
+        if (d.frame_same) d.frame_same[e] = (uint8_t)(d.ovr_slot[e] < 0 && d.frame_cached[e]);
         d.reset_set[e] = 0; d.ovr_slot[e] = -1;
         d.feature[e * 2] = 0.0f; d.feature[e * 2 + 1] = 0.0f;
         return;
@@ -442,6 +452,11 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
     const double max_fwd = d.params[MWB_P_FORWARD_STEP].hi[0];   // self.max_forward_step
     const double cam_height = d.cam[e * 4 + 0];
     const int ns = d.n_segs[e];
+    // The frame on record can stand for this step's only if the step writes nothing a frame depends on: a blocked move (or no
+    // action at all) with nothing carried before or after - then no entity moved and neither task rule below touched the list
+    // (CollectHealth's health ticks down, which no frame shows).  An override of the step BEFORE rules it out too: that step's
+    // frame shows an entity where the state no longer has it.
+    bool same = carried < 0 && d.ovr_slot[e] < 0;
     d.ovr_slot[e] = -1;
     MtSerial g;
     const bool use_rng = d.domain_rand || d.task == MWB_TASK_COLLECTHEALTH;
@@ -507,8 +522,9 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
             if (intersect(carried, cx, cz, cr, f32)) hit = true;
             else set_pose(carried, cx, cy, cz, false);
         }
-        if (!hit) { ax = nx; az = nz; d.agent_x[e] = ax; d.agent_z[e] = az; }
+        if (!hit) { ax = nx; az = nz; d.agent_x[e] = ax; d.agent_z[e] = az; same = false; }
     } else if (a == 0 || a == 1) {   // turn_agent, miniworld.py:635-656
+        same = false;
         double ta = (a == 0) ? turn_step : -turn_step;
         ta *= (3.141592653589793 / 180);
         const double orig = adir;
@@ -529,6 +545,7 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
     } else if (a == 5) {   // drop, miniworld.py:692-695
         if (carried >= 0) { d.box_y[(size_t)carried * N + e] = 0.0; carried = -1; }
     }
+    if (carried >= 0) same = false;   // picked up just now (carried before: ruled out above)
     if (carried >= 0) {   // miniworld.py:698-701
         double cx, cy, cz;
         carry_pos(carried, ax, az, adir, cx, cy, cz);
@@ -618,6 +635,7 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
     const bool regen = done && d.auto_reset;
     d.reset_set[e] = (uint8_t)regen;
     if (regen) d.reset_list[atomicAdd(d.reset_count, 1)] = e;
+    if (d.frame_same) d.frame_same[e] = (uint8_t)(same && !regen && d.ovr_slot[e] < 0 && d.frame_cached[e]);
 }
 
 __global__ void mark_reset_kernel(MwbDev d, const uint8_t *__restrict__ mask) {
@@ -3116,20 +3134,68 @@ struct RenderCtx {
 #define QUEUE_CAP 128
 #define ITEM_RES_BYTES(W) ((((W) + TILE_CX - 2) / (TILE_CX - 1)) * 4 * 16)   // n_strips x 4 quarters x uint4
 
-// LDS -> HBM copy of the byte range [begin, end) of the frame with the widest vectors its alignment allows
+// LDS -> HBM copy of the byte range [begin, end) of the frame with the widest vectors its alignment allows; dst2: a second
+// destination of the same bytes (the env's last-frame cache) or null
 template <int THREADS>
-__device__ __forceinline__ void copy_frame_range(uint8_t *__restrict__ dst, const uint8_t *__restrict__ fb, int begin, int end, int tid) {
+__device__ __forceinline__ void copy_frame_range(uint8_t *__restrict__ dst, const uint8_t *__restrict__ fb, int begin, int end, int tid,
+                                                 uint8_t *__restrict__ dst2 = nullptr) {
     if (((begin | end) & 15) == 0) {
         const uint4 *s4 = (const uint4 *)fb;
-        uint4 *d4 = (uint4 *)dst;
-        for (int i = begin / 16 + tid; i < end / 16; i += THREADS) d4[i] = s4[i];
+        uint4 *d4 = (uint4 *)dst, *e4 = (uint4 *)dst2;
+        for (int i = begin / 16 + tid; i < end / 16; i += THREADS) { const uint4 v = s4[i]; d4[i] = v; if (dst2) e4[i] = v; }
     } else if (((begin | end) & 3) == 0) {
         const uint32_t *s1 = (const uint32_t *)fb;
-        uint32_t *d1 = (uint32_t *)dst;
-        for (int i = begin / 4 + tid; i < end / 4; i += THREADS) d1[i] = s1[i];
+        uint32_t *d1 = (uint32_t *)dst, *e1 = (uint32_t *)dst2;
+        for (int i = begin / 4 + tid; i < end / 4; i += THREADS) { const uint32_t v = s1[i]; d1[i] = v; if (dst2) e1[i] = v; }
     } else {
-        for (int i = begin + tid; i < end; i += THREADS) dst[i] = fb[i];
+        for (int i = begin + tid; i < end; i += THREADS) { const uint8_t v = fb[i]; dst[i] = v; if (dst2) dst2[i] = v; }
     }
+}
+
+// Fused frame stack: the bytes [b0, b1) of a CWH frame (`src`: the LDS framebuffer, or the last-frame cache) into the newest
+// three planes of an env's window, whose first element is env_base - u8 -> f32 on the way when the stack is float
+template <int THREADS>
+__device__ __forceinline__ void stack_put_range(const MwbDev &d, size_t env_base, const uint8_t *__restrict__ src, int b0, int b1, int tid) {
+    const size_t dst0 = env_base + (size_t)(d.stk_C - 3) * (d.W * d.H);
+    if (d.stk_float) {
+        float *o = (float *)d.stk + dst0;
+        if (((b0 | b1) & 3) == 0) {
+            for (int i = b0 / 4 + tid; i < b1 / 4; i += THREADS) {
+                const uint32_t p = ((const uint32_t *)src)[i];
+                ((float4 *)o)[i] = make_float4((float)(p & 255u), (float)((p >> 8) & 255u), (float)((p >> 16) & 255u), (float)(p >> 24));
+            }
+        } else {
+            for (int i = b0 + tid; i < b1; i += THREADS) o[i] = (float)src[i];
+        }
+    } else {
+        copy_frame_range<THREADS>((uint8_t *)d.stk + dst0, src, b0, b1, tid);
+    }
+}
+
+// The way into the last-frame cache for the frame of a regenerated env (side-stream pass): copied from the outputs its workgroup
+// has just written, after a barrier, by a call that is not inlined - nothing of it is hoisted out of the loop around render_env
+// and kept alive across whole frames (inlined, or stored from LDS inside render_env: 104 - 170 B/lane of scratch, budget 96)
+template <int THREADS>
+__device__ __noinline__ void keep_frame(uint8_t *frame_keep, const uint8_t *frame, int nbytes, uint8_t *depth_keep, const uint8_t *depth, int zbytes, uint8_t *cached) {
+    const int tid = threadIdx.x;
+    copy_frame_range<THREADS>(frame_keep, frame, 0, nbytes, tid);
+    if (depth_keep) copy_frame_range<THREADS>(depth_keep, depth, 0, zbytes, tid);
+    if (tid == 0) *cached = 1;
+}
+// The bulk pass' answer for an env whose step changed nothing its frame depends on (d.frame_same): the frame of the step before,
+// from the private cache into the outputs - and into the fused stack's window, as the newest frame - instead of a render.
+template <int THREADS>
+__device__ __forceinline__ void reuse_frame(const MwbDev &d, const int e) {
+    const int tid = threadIdx.x;
+    const int nbytes = d.W * d.H * 3;
+    const uint8_t *src = d.frame_cache + (size_t)e * nbytes;
+    copy_frame_range<THREADS>(d.obs + (size_t)e * nbytes, src, 0, nbytes, tid);
+    if (d.want_depth) {
+        const size_t o = (size_t)e * d.W * d.H;
+        copy_frame_range<THREADS>((uint8_t *)(d.depth + o), (const uint8_t *)(d.depth_cache + o), 0, d.W * d.H * 4, tid);
+    }
+    if (d.stk && d.layout == MWB_LAYOUT_CWH)
+        stack_put_range<THREADS>(d, ((size_t)e * d.stk_K + d.stk_pos) * (d.W * d.H), src, 0, nbytes, tid);
 }
 
 // Renders one env with the whole workgroup (called once per workgroup, or per list entry on the side stream).
@@ -3583,6 +3649,12 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
     {   // framebuffer LDS -> HBM, 16 bytes per lane where the alignment allows
         const int nbytes = W * H * 3;
         uint8_t *dst = d.obs + (size_t)e * nbytes;
+        // the env's last-frame cache gets the frame too (a regenerated env's - LOOPED - is copied by the caller: keep_frame)
+        uint8_t *keep = (!TILED && !LOOPED && d.frame_cache) ? d.frame_cache + (size_t)e * nbytes : nullptr;
+        // The depth map went to HBM pixel by pixel (RenderCtx is full): the cache gets this workgroup's part of it read back - its
+        // own waves' stores, ordered before these loads by the barrier above.  [H][W] floats whatever the frame's layout.
+        const uint8_t *zsrc = (keep && d.want_depth) ? (const uint8_t *)(d.depth + (size_t)e * W * H) : nullptr;
+        uint8_t *zkeep = zsrc ? (uint8_t *)(d.depth_cache + (size_t)e * W * H) : nullptr;
         if (TILED) {
             if (d.layout == MWB_LAYOUT_HWC) {   // the tile's rows into the big frame
                 uint8_t *big = d.obs + ((size_t)e * d.W * d.H + (size_t)ty0 * d.W + tx0) * 3;
@@ -3598,16 +3670,26 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
                 }
             }
         } else if (part < 0) {
-            copy_frame_range<THREADS>(dst, fb, 0, nbytes, tid);
+            copy_frame_range<THREADS>(dst, fb, 0, nbytes, tid, keep);
+            if (zsrc) copy_frame_range<THREADS>(zkeep, zsrc, 0, W * H * 4, tid);
         } else if (!split_x) {   // HWC: rows [r0, r1)
             const int mid = 2 * part_h < H ? 2 * part_h : H;
             const int r0 = part ? mid : 0, r1 = part ? H : mid;
-            copy_frame_range<THREADS>(dst, fb, r0 * W * 3, r1 * W * 3, tid);
+            copy_frame_range<THREADS>(dst, fb, r0 * W * 3, r1 * W * 3, tid, keep);
+            if (zsrc) copy_frame_range<THREADS>(zkeep, zsrc, r0 * W * 4, r1 * W * 4, tid);
         } else {                 // CWH: columns [xa, xb) of each channel plane
             const int midx = half_strips * (TILE_CX - 1) < W ? half_strips * (TILE_CX - 1) : W;
             const int xa = part ? midx : 0, xb = part ? W : midx;
-            for (int q = 0; q < 3; q++) copy_frame_range<THREADS>(dst, fb, (q * W + xa) * H, (q * W + xb) * H, tid);
+            for (int q = 0; q < 3; q++) copy_frame_range<THREADS>(dst, fb, (q * W + xa) * H, (q * W + xb) * H, tid, keep);
+            if (zsrc) {
+                const int wx = xb - xa;
+                for (int i = tid; i < H * wx; i += THREADS) {
+                    const int y = i / wx, o = y * W + xa + (i - y * wx);
+                    ((float *)zkeep)[o] = ((const float *)zsrc)[o];
+                }
+            }
         }
+        if (keep && tid == 0) d.frame_cached[e] = 1;   // read by the NEXT step's kernel (both halves of a split frame write it)
         // Fused frame stack (mwb_stack_enable with MWB_STACK_FUSED; CWH frames): the new frame also goes straight into the
         // newest three planes of the env's sliding window - u8 -> f32 on the way out of LDS - and an env that was
         // regenerated in this pass gets its history planes zeroed (VecPyTorchFrameStack, envs.py:149-156): no stack pass.
@@ -3622,23 +3704,8 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
                 if (d.stk_float) { float4 *z = (float4 *)((float *)d.stk + env_base); for (int i = i0 + tid; i < i1; i += THREADS) z[i] = make_float4(0, 0, 0, 0); }
                 else { uint32_t *z = (uint32_t *)((uint8_t *)d.stk + env_base); for (int i = i0 + tid; i < i1; i += THREADS) z[i] = 0u; }
             }
-            for (int q = 0; q < 3; q++) {
-                const int b0 = (q * W + xa) * H, b1 = (q * W + xb) * H;   // byte range of this channel plane's columns in fb (multiples of 4: W*H % 4 == 0 checked, H*15 ... see host check)
-                const size_t dst0 = env_base + (size_t)(C - 3) * plane;
-                if (d.stk_float) {
-                    float *o = (float *)d.stk + dst0;
-                    if (((b0 | b1) & 3) == 0) {
-                        for (int i = b0 / 4 + tid; i < b1 / 4; i += THREADS) {
-                            const uint32_t p = ((const uint32_t *)fb)[i];
-                            ((float4 *)o)[i] = make_float4((float)(p & 255u), (float)((p >> 8) & 255u), (float)((p >> 16) & 255u), (float)(p >> 24));
-                        }
-                    } else {
-                        for (int i = b0 + tid; i < b1; i += THREADS) o[i] = (float)fb[i];
-                    }
-                } else {
-                    copy_frame_range<THREADS>((uint8_t *)d.stk + dst0, fb, b0, b1, tid);
-                }
-            }
+            for (int q = 0; q < 3; q++)   // byte range of this channel plane's columns in fb (multiples of 4: W*H % 4 == 0 checked, H*15 ... see host check)
+                stack_put_range<THREADS>(d, env_base, fb, (q * W + xa) * H, (q * W + xb) * H, tid);
         }
     }
 }
@@ -3656,6 +3723,12 @@ __global__ void __launch_bounds__(THREADS, NBOX > MWB_MAX_BOXES ? ENT_WGS_PER_CU
         for (int li = blockIdx.x; li < count; li += gridDim.x) {
             render_env<THREADS, NBOX, true, POLY>(d, d.reset_list[li], -1, smem);
             __syncthreads();   // LDS is reused by the next env of this block
+            if (d.frame_cache) {
+                const size_t e = (size_t)d.reset_list[li], px = (size_t)d.W * d.H;
+                keep_frame<THREADS>(d.frame_cache + e * px * 3, d.obs + e * px * 3, (int)px * 3, d.want_depth ? (uint8_t *)(d.depth_cache + e * px) : nullptr,
+                                    d.want_depth ? (const uint8_t *)(d.depth + e * px) : nullptr, (int)px * 4, d.frame_cached + e);
+            }
+            if (d.reuse_pass && threadIdx.x == 0) atomicAdd(d.reuse_stats + 1, 1ull);
         }
     } else {
         // Workgroups take the envs in the order of decreasing cost measured by the previous launch (frames change
@@ -3668,6 +3741,13 @@ __global__ void __launch_bounds__(THREADS, NBOX > MWB_MAX_BOXES ? ENT_WGS_PER_CU
         const int part = b < whole ? -1 : ((b - whole) & 1);
         const int e = __builtin_amdgcn_readfirstlane(d.order_bufs[d.order_state[0] & 1][slot]);
         if (MODE == 2 && d.reset_set[e]) return;   // block-uniform
+        if (d.reuse_pass && d.frame_same && d.frame_same[e]) {   // block-uniform; decided by this step's step kernel (never for a regenerated env)
+            if (part <= 0) {   // of a half-frame pair the first copies the frame, the second has nothing to do
+                reuse_frame<THREADS>(d, e);
+                if (threadIdx.x == 0) atomicAdd(d.reuse_stats, 1ull);
+            }
+            return;   // d.cost[e] keeps the last measured cost: order_kernel does not file the env under "cheapest"
+        }
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();   // read by every wave: stays in scalar registers
         render_env<THREADS, NBOX, false, POLY>(d, e, part, smem);
         if (threadIdx.x == 0) {
@@ -3676,6 +3756,7 @@ __global__ void __launch_bounds__(THREADS, NBOX > MWB_MAX_BOXES ? ENT_WGS_PER_CU
             const uint32_t dt = (uint32_t)(t1 - t0);
             if (part < 0) { d.cost[2 * e] = dt; d.cost[2 * e + 1] = 0; }
             else d.cost[2 * e + part] = dt;
+            if (d.reuse_pass && part <= 0) atomicAdd(d.reuse_stats + 1, 1ull);   // here, not ahead of the frame: there it cost 136 B/lane of spills
         }
     }
 }

@@ -251,6 +251,13 @@ int mwb_step(mwb_handle *h, const int32_t *actions_dev, const uint8_t *skip_mask
 int mwb_step_i64(mwb_handle *h, const int64_t *actions_dev, const uint8_t *skip_mask_dev, void *stream);
 /* replaces: MiniWorldEnv.render_obs / render_depth (miniworld.py:1160-1220) for the whole batch */
 int mwb_render(mwb_handle *h, void *stream);
+/* Last-frame reuse.  A step that leaves an env exactly as it was - a move that a wall or an entity blocks, nothing carried; an env
+ * the skip mask leaves out - would render the frame of the step before once more.  The handle keeps every env's last frame in a
+ * private cache (N x W*H*3 bytes, + N x W*H*4 with depth) and the step's bulk pass copies it into the outputs instead; the
+ * outputs stay the caller's to overwrite, every step rewrites them in full.  mwb_reset and mwb_render always render.  The
+ * environment variable MWB_NO_FRAME_REUSE=1 at mwb_create turns it off (no cache is allocated); it is off as well for frames
+ * rendered in tiles.  out: frames the step passes reused / rendered since the last call.  Synchronous. */
+int mwb_frame_reuse_stats(mwb_handle *h, unsigned long long out[2]);
 int mwb_get_outputs(mwb_handle *h, mwb_outputs *out);
 
 /* ---- learner-side layout fusion ---------------------------------------- */
