@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "mwb_internal.h"
+#include "mwb_texture_host.h"
 
 static thread_local std::string g_err;
 static int set_err(int code, const std::string &msg) { g_err = msg; return code; }
@@ -429,43 +430,7 @@ extern "C" int mwb_destroy(mwb_handle *h) {
 }
 
 // ------------------------------------------------------------------------------------ textures
-// Mip chain: level k+1 has dims max(1, n/2); each texel is the equal-weight mean (round half up) of
-// the source texels it covers - 2x2 for even sizes (DESIGN.md render spec; restates
-// glGenerateMipmap of opengl.py:98-99, whose filter GL leaves to the driver).
-static void build_mips(const uint8_t *rgb, int w, int h, std::vector<std::vector<uint32_t>> &levels) {
-    levels.clear();
-    std::vector<uint32_t> cur((size_t)w * h);
-    for (int y = 0; y < h; y++)   // flip: texture row 0 = bottom image row (pyglet upload order, opengl.py:85-96)
-        for (int x = 0; x < w; x++) {
-            const uint8_t *p = rgb + ((size_t)(h - 1 - y) * w + x) * 3;
-            cur[(size_t)y * w + x] = p[0] | (p[1] << 8) | (p[2] << 16) | 0xFF000000u;
-        }
-    levels.push_back(cur);
-    int sw = w, sh = h;
-    while (sw > 1 || sh > 1) {
-        int dw = sw > 1 ? sw / 2 : 1, dh = sh > 1 ? sh / 2 : 1;
-        std::vector<uint32_t> nxt((size_t)dw * dh);
-        const std::vector<uint32_t> &src = levels.back();
-        for (int j = 0; j < dh; j++) {
-            int j0 = (int)(((long long)j * sh) / dh), j1 = (int)((((long long)(j + 1) * sh) + dh - 1) / dh);
-            for (int i = 0; i < dw; i++) {
-                int i0 = (int)(((long long)i * sw) / dw), i1 = (int)((((long long)(i + 1) * sw) + dw - 1) / dw);
-                uint32_t sum[4] = {0, 0, 0, 0};
-                for (int y = j0; y < j1; y++)
-                    for (int x = i0; x < i1; x++) {
-                        uint32_t t = src[(size_t)y * sw + x];
-                        sum[0] += t & 255u; sum[1] += (t >> 8) & 255u; sum[2] += (t >> 16) & 255u; sum[3] += t >> 24;
-                    }
-                uint32_t cnt = (uint32_t)((j1 - j0) * (i1 - i0));
-                uint32_t o = 0;
-                for (int c = 0; c < 4; c++) o |= ((sum[c] + cnt / 2) / cnt) << (8 * c);
-                nxt[(size_t)j * dw + i] = o;
-            }
-        }
-        levels.push_back(nxt);
-        sw = dw; sh = dh;
-    }
-}
+// build_mips and the footprint tables: mwb_texture_host.h
 
 extern "C" int mwb_set_texture(mwb_handle *h, int tex_id, int width, int height, const uint8_t *rgb) {
     if (!h || !rgb) return set_err(MWB_EINVAL, "mwb_set_texture: null argument");
@@ -484,16 +449,21 @@ static int upload_textures(mwb_handle *h) {
     for (int i = 0; i < n_tex; i++)
         if (h->tex_w[i] == 0)
             return set_err(MWB_ESTATE, "render requested before the task's " + std::to_string(n_tex) + " textures were set (mwb_set_texture)");
+    // one footprint table per mip level: (w+1) x (h+1) entries of the four wrapped texels of a bilinear tap (mwb_texture_host.h).
+    // The kernels address entries with 32-bit byte offsets from the buffer's base.
+    size_t total = 0;
+    for (int i = 0; i < n_tex; i++) total += pyramid_footprint_entries(h->tex_w[i], h->tex_h[i]);
+    if (total * 16 > 0xFFFFFFFFull)
+        return set_err(MWB_EINVAL, "textures too large: the footprint tables take " + std::to_string(total * 16) +
+                                       " bytes, byte offsets into them must fit 32 bits");
     std::vector<uint32_t> all;
+    all.reserve(total * 4);
     MwbTexDesc desc[MWB_MAX_TEX];
     memset(desc, 0, sizeof(desc));
     for (int i = 0; i < n_tex; i++) {
         desc[i].w = h->tex_w[i]; desc[i].h = h->tex_h[i]; desc[i].n_levels = (int)h->tex_levels[i].size();
         desc[i].sc_s = (float)(512.0 / h->tex_w[i]); desc[i].sc_t = (float)(512.0 / h->tex_h[i]);
-        for (size_t l = 0; l < h->tex_levels[i].size(); l++) {
-            desc[i].level_off[l] = (uint32_t)all.size();
-            all.insert(all.end(), h->tex_levels[i][l].begin(), h->tex_levels[i][l].end());
-        }
+        append_pyramid_footprints(h->tex_levels[i], h->tex_w[i], h->tex_h[i], desc[i].level_off, all);
     }
     HIP_TRY(hipDeviceSynchronize());
     if (h->texels_dev) { hipFree(h->texels_dev); h->texels_dev = nullptr; }

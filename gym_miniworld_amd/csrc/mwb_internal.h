@@ -128,7 +128,7 @@ struct MwbTexDesc {
     int w, h, n_levels;
     float sc_s, sc_t;                     // TEX_DENSITY / size (miniworld.py:17,30-31,58-63) as f32
     int pad[3];
-    uint32_t level_off[MWB_MAX_LEVELS];   // texel (u32) offsets into the shared texel buffer
+    uint32_t level_off[MWB_MAX_LEVELS];   // first entry of the level's footprint table, in 16-byte entries of the shared texel buffer
 };
 
 struct MwbParam { double def[3], lo[3], hi[3]; };

@@ -2276,21 +2276,24 @@ static_assert(sizeof(TexLds) == sizeof(MwbTexDesc), "TexLds mirrors MwbTexDesc")
 // No "fp contract(fast)" here: which products the compiler fuses would depend on the code around each inlined copy, and
 // the interior-pixel path must produce the very bits the 8-sample path produces for the same surface
 // (test_fast_path_equals_full_sample_path).  Every fused multiply-add below is written out.
-__device__ __forceinline__ void bilinear(const uint32_t *__restrict__ texels, uint32_t off, int w, int h, float s, float t, float *rgb) {
+// One bilinear tap is one 16-byte load: the host builds, per mip level, a table of (w+1) x (h+1) entries holding the four
+// GL_REPEAT-wrapped texels of the footprint whose lower-left texel is (i0, j0) in [-1, w-1] x [-1, h-1] (mwb_texture_host.h),
+// so the kernel computes no wrap, no second row and one address.  footprint_index: the weights' fractions and the entry.
+__device__ __forceinline__ uint32_t footprint_index(uint32_t off, int w, int h, float s, float t, float &a, float &b) {
     float uu = fmaf(s, (float)w, -0.5f), vv = fmaf(t, (float)h, -0.5f);
     float fu = floorf(uu), fv = floorf(vv);
-    float a = uu - fu, b = vv - fv;
+    a = uu - fu; b = vv - fv;
     int i0 = (int)fu, j0 = (int)fv;
-    // s,t in [0,1): i0 in [-1, w-1]; wrap with compares instead of integer division
-    int i1 = i0 + 1; if (i1 >= w) i1 -= w; if (i0 < 0) i0 += w;
-    int j1 = j0 + 1; if (j1 >= h) j1 -= h; if (j0 < 0) j0 += h;
-    // unsigned 32-bit texel indices (24-bit multiplies: levels are at most 1024 wide) keep the address math
-    // out of 64-bit VALU arithmetic: the loads use the scalar base + 32-bit offset form
-    // (the pyramids total ~14 MB, so byte offsets fit 32 bits)
-    const uint32_t r0 = off + __umul24((uint32_t)j0, (uint32_t)w), r1 = off + __umul24((uint32_t)j1, (uint32_t)w);
-    const char *tb = (const char *)texels;
-    auto texel = [tb](uint32_t idx) { return *(const uint32_t *)(tb + (size_t)(idx << 2)); };
-    uint32_t t00 = texel(r0 + (uint32_t)i0), t10 = texel(r0 + (uint32_t)i1), t01 = texel(r1 + (uint32_t)i0), t11 = texel(r1 + (uint32_t)i1);
+    // s,t in [0,1): i0 in [-1, w-1], j0 in [-1, h-1].  Unsigned 32-bit entry indices (24-bit multiplies: levels are at most
+    // 2048 wide) keep the address math out of 64-bit VALU arithmetic: the loads use the scalar base + 32-bit offset form
+    // (upload_textures refuses tables whose byte offsets do not fit 32 bits)
+    return off + __umul24((uint32_t)(j0 + 1), (uint32_t)(w + 1)) + (uint32_t)(i0 + 1);
+}
+__device__ __forceinline__ uint4 footprint_load(const uint32_t *__restrict__ texels, uint32_t idx) {
+    return *(const uint4 *)((const char *)texels + (size_t)(idx << 4));
+}
+__device__ __forceinline__ void bilinear_blend(const uint4 fp, float a, float b, float *rgb) {
+    const uint32_t t00 = fp.x, t10 = fp.y, t01 = fp.z, t11 = fp.w;
     float w00 = (1.0f - a) * (1.0f - b), w10 = a * (1.0f - b), w01 = (1.0f - a) * b, w11 = a * b;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -2321,15 +2324,19 @@ __device__ __forceinline__ void sample_texture(const uint32_t *__restrict__ texe
     int l0 = (int)fl; l0 = l0 > maxl ? maxl : l0;
     const int l1 = l0 + 1 > maxl ? maxl : l0 + 1;
     const float fr = (l0 == maxl) ? 0.0f : lambda - fl;
-    // both levels are always fetched (l1 == l0 when there is nothing to blend) so that the eight texel
+    // both levels are always fetched (l1 == l0 when there is nothing to blend) so that the two footprint
     // loads are issued together and waited for once
     float c0[3], c1[3];
     int w0 = dims.x >> l0; w0 = w0 < 1 ? 1 : w0;
     int h0 = dims.y >> l0; h0 = h0 < 1 ? 1 : h0;
     int w1 = dims.x >> l1; w1 = w1 < 1 ? 1 : w1;
     int h1 = dims.y >> l1; h1 = h1 < 1 ? 1 : h1;
-    bilinear(texels, T.off[l0], w0, h0, ws, wt, c0);
-    bilinear(texels, T.off[l1], w1, h1, ws, wt, c1);
+    float a0, b0, a1, b1;
+    const uint32_t e0 = footprint_index(T.off[l0], w0, h0, ws, wt, a0, b0);
+    const uint32_t e1 = footprint_index(T.off[l1], w1, h1, ws, wt, a1, b1);
+    const uint4 f0 = footprint_load(texels, e0), f1 = footprint_load(texels, e1);
+    bilinear_blend(f0, a0, b0, c0);
+    bilinear_blend(f1, a1, b1, c1);
 #pragma unroll
     for (int k = 0; k < 3; k++) rgb[k] = fmaf(c1[k] - c0[k], fr, c0[k]);
 }
