@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "mwb_internal.h"
+#include "mwb_lds_layout.h"
 #include "mwb_texture_host.h"
 
 static thread_local std::string g_err;
@@ -384,14 +385,11 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
         return set_err(MWB_EHIP, "mwb_create: could not create the side stream / events");
     }
     for (int i = 0; i < MWB_MAX_TEX; i++) { h->tex_w[i] = 0; h->tex_h[i] = 0; }
-    if (d.tile_w == 0) {   // an observation that does not fit one workgroup's LDS (or its 16-bit pixel queue) is rendered in tiles, like mwb_render_view's frames
-        int wshift = 0;
-        while ((1 << wshift) < d.W) wshift++;
-        if (mwb_render_lds_bytes(d) > 160 * 1024 || ((size_t)d.H << wshift) > 65536) {
-            int tw = 0, th = 0;
-            mwb_view_tile(&tw, &th);
-            d.tile_w = tw < d.W ? tw : d.W; d.tile_h = th < d.H ? th : d.H;
-        }
+    // an observation that does not fit one workgroup's LDS (or its 16-bit pixel queue) is rendered in tiles, like mwb_render_view's frames
+    if (d.tile_w == 0 && (mwb_render_lds_bytes(d) > 160 * 1024 || !mwb_pixel_queue_fits(d.W, d.H))) {
+        int tw = 0, th = 0;
+        mwb_view_tile(&tw, &th);
+        d.tile_w = tw < d.W ? tw : d.W; d.tile_h = th < d.H ? th : d.H;
     }
     // last-frame reuse: N x (W*H*3 [+ W*H*4 with depth]) bytes of cache and two flags per env; MWB_NO_FRAME_REUSE=1 turns it off
     { const char *no = getenv("MWB_NO_FRAME_REUSE"); h->frame_reuse = !(no && atoi(no)) && d.tile_w == 0; }

@@ -13,10 +13,11 @@
 // Compiled with -ffp-contract=off: world generation and the step must reproduce the reference's
 // float64 results bit for bit, and the visibility arithmetic of the renderer is specified with
 // explicit fmaf() ("render spec").
+#include <type_traits>
+
 #include "mwb_internal.h"
 #include "mwb_glibc_trig.h"
-
-#define WAVE 64
+#include "mwb_lds_layout.h"
 
 // float64 sin / cos as the reference's process computes them (math.sin / math.cos -> glibc 2.35 __sin_fma / __cos_fma,
 // restated bit for bit in mwb_glibc_trig.h); OCML's differ in the last bit for a few arguments in a thousand, which an
@@ -676,6 +677,8 @@ struct alignas(16) WRoom {
     int ne, pad_;                   // num_walls: 4, or 3 for YMaze's triangular hub
 };
 
+static_assert(sizeof(WRoom) == MWB_WROOM_BYTES, "mwb_lds_layout.h sizes reset_kernel's room store with MWB_WROOM_BYTES");
+
 typedef LDS_AS WRoom LRoom;
 
 enum { TEXF_FLOOR_TILES_BW = 0, TEXF_CONCRETE, TEXF_CONCRETE_TILES, TEXF_BRICK_WALL,
@@ -1073,18 +1076,18 @@ __global__ void __launch_bounds__(WAVE) reset_kernel(MwbDev d) {
     const int e = d.reset_list[li];
     __syncthreads();   // LDS is reused from the previous env of this block
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    LRoom *rooms = (LRoom *)smem;
-    size_t off = (size_t)d.R_max * sizeof(WRoom);
-    lds_f64 *cdf = (lds_f64 *)(smem + off); off += (size_t)d.R_max * sizeof(double);
-    lds_i32 *seg_off = (lds_i32 *)(smem + off); off += (size_t)((d.R_max + 3) & ~3) * sizeof(int);
-    lds_u32 *key = (lds_u32 *)(smem + off); off += 624 * sizeof(uint32_t);
-    // Maze: the frames of the depth-first search (3 ints per cell + 1) and the visited flags; entity tasks: per slot x y z dir size
-    // radius height scale bias[3] (f64) and meta, radius-is-float32, colour index (i32), text textures.  (mwb_reset_lds_bytes)
-    lds_i32 *dfs = (lds_i32 *)(smem + off);
-    lds_f64 *E_x = (lds_f64 *)(smem + off), *E_y = E_x + MWB_MAX_ENTS, *E_z = E_y + MWB_MAX_ENTS, *E_dir = E_z + MWB_MAX_ENTS,
-           *E_size = E_dir + MWB_MAX_ENTS, *E_rad = E_size + MWB_MAX_ENTS, *E_hgt = E_rad + MWB_MAX_ENTS, *E_scale = E_hgt + MWB_MAX_ENTS,
-           *E_bias = E_scale + MWB_MAX_ENTS;
-    lds_i32 *E_meta = (lds_i32 *)(E_bias + 3 * MWB_MAX_ENTS), *E_f32 = E_meta + MWB_MAX_ENTS, *E_col = E_f32 + MWB_MAX_ENTS, *E_text = E_col + MWB_MAX_ENTS;
+    const ResetLds L = reset_lds(d.R_max, d.ent_task != 0, TASK_ == MWB_TASK_MAZE);   // mwb_lds_layout.h
+    LRoom *rooms = (LRoom *)(smem + L.rooms);
+    lds_f64 *cdf = (lds_f64 *)(smem + L.cdf);
+    lds_i32 *seg_off = (lds_i32 *)(smem + L.seg_off);
+    lds_u32 *key = (lds_u32 *)(smem + L.key);
+    // Maze: the frames of the depth-first search and the visited flags; entity tasks: per slot x y z dir size radius height scale
+    // bias[3] (f64) and meta, radius-is-float32, colour index (i32), text textures
+    lds_i32 *dfs = (lds_i32 *)(smem + L.dfs);
+    lds_f64 *E_x = (lds_f64 *)(smem + L.e_x), *E_y = (lds_f64 *)(smem + L.e_y), *E_z = (lds_f64 *)(smem + L.e_z), *E_dir = (lds_f64 *)(smem + L.e_dir),
+            *E_size = (lds_f64 *)(smem + L.e_size), *E_rad = (lds_f64 *)(smem + L.e_rad), *E_hgt = (lds_f64 *)(smem + L.e_hgt),
+            *E_scale = (lds_f64 *)(smem + L.e_scale), *E_bias = (lds_f64 *)(smem + L.e_bias);
+    lds_i32 *E_meta = (lds_i32 *)(smem + L.e_meta), *E_f32 = (lds_i32 *)(smem + L.e_f32), *E_col = (lds_i32 *)(smem + L.e_col), *E_text = (lds_i32 *)(smem + L.e_text);
     // The collision segments are staged in HBM, one row set per block (8 KB of Maze's LDS: the difference between three and four
     // workgroups per CU); the placement loop reads them lane-parallel, coalesced, out of L1 / L2.
     double *segs = d.seg_stage + (size_t)blockIdx.x * d.S_max * 4;
@@ -1437,7 +1440,7 @@ __global__ void __launch_bounds__(WAVE) reset_kernel(MwbDev d) {
             }
         // DFS frames: cell, packed neighbour order, next index
         lds_i32 *stack = dfs;
-        LDS_AS uint8_t *visited = (LDS_AS uint8_t *)(stack + 3 * (num_rows * num_cols + 1));
+        LDS_AS uint8_t *visited = (LDS_AS uint8_t *)(stack + 3 * (num_rows * num_cols + 1));   // the split ResetLds::dfs is sized for (from R_max there: 151 -> 147 AGPRs here)
         for (int i = 0; i < num_rows * num_cols; i++) visited[i] = 0;
         __syncthreads();
         int sp = 0;
@@ -2224,10 +2227,6 @@ __device__ __forceinline__ bool mesh_tri(const float *lo, const float *ld, const
 }
 // nearest front-facing triangle of the entity's mesh along (eye, dv) that is strictly nearer than t_max: its index in draw order
 // or -1.  Threaded BVH (host-built, gym_miniworld_amd/meshes.py): depth-first node order, `skip` links, no stack.
-#define MQ_CAP 320     // mesh-pixel queue entries per wave: batches wait for the end of the frame, where all waves share them
-#define MB_HALF 4      // pixels_mesh: samples per round
-#define MB_TASKS 320   //   (ray, mesh) pairs per round
-#define MB_WAVE_BYTES (MB_HALF * 64 * 8 + MB_TASKS * 2 + 64 * 4 + 16)   // per wave: slots, pairs, pixel coordinates, counter
 typedef float f4n __attribute__((ext_vector_type(4)));   // a plain 16-byte vector for the mesh records (walk_meshes)
 // ImageFrame / TextFrame: slab [0, depth] x [-h/2, h/2] x [-w/2, w/2] in the frame's axes; returns the character cell of the
 // front (+x) face, 100 for a black side, -1 for a miss or the missing back
@@ -2272,6 +2271,7 @@ __device__ __forceinline__ bool frame_front_tc(const float *blk, int cell, const
 // ---- shading: continuous in its inputs, so fused / approximate arithmetic is within the +-1 LSB bar
 struct TexLds { int w, h, n_levels; float sc_s, sc_t; int pad[3]; uint32_t off[MWB_MAX_LEVELS]; };
 static_assert(sizeof(TexLds) == sizeof(MwbTexDesc), "TexLds mirrors MwbTexDesc");
+static_assert(sizeof(TexLds) == MWB_TEX_LDS_BYTES, "mwb_lds_layout.h sizes the descriptors' region with MWB_TEX_LDS_BYTES");
 
 // No "fp contract(fast)" here: which products the compiler fuses would depend on the code around each inlined copy, and
 // the interior-pixel path must produce the very bits the 8-sample path produces for the same surface
@@ -2395,11 +2395,7 @@ struct RenderCtx {
 #pragma unroll
         for (int k = 0; k < 3; k++) { dx[k] = fmaf(cam.S[k], sx, dc[k]); dy[k] = fmaf(cam.U[k], sy, dc[k]); }
     }
-    __device__ __forceinline__ void neighbour_rays(const float *dc, float *dx, float *dy) const {
-        const float sx = 2.0f * cam.invW * cam.TW, sy = 2.0f * cam.invH * cam.TH;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { dx[k] = fmaf(cam.S[k], sx, dc[k]); dy[k] = fmaf(cam.U[k], sy, dc[k]); }
-    }
+    __device__ __forceinline__ void neighbour_rays(const float *dc, float *dx, float *dy) const { neighbour_rays_of(cam, dc, dx, dy); }
 
     template <bool PATH>
     __device__ __forceinline__ uint32_t trace_from(int room, const float *dv, float &t_hit, uint32_t &path) const {
@@ -3136,11 +3132,6 @@ struct RenderCtx {
     }
 };
 
-#define TILE_CX 16   // corner grid of one wave pass: 16 x 4 corners; marching down a strip it classifies 15 x 4 pixels
-#define TILE_CY 4
-#define QUEUE_CAP 128
-#define ITEM_RES_BYTES(W) ((((W) + TILE_CX - 2) / (TILE_CX - 1)) * 4 * 16)   // n_strips x 4 quarters x uint4
-
 // LDS -> HBM copy of the byte range [begin, end) of the frame with the widest vectors its alignment allows; dst2: a second
 // destination of the same bytes (the env's last-frame cache) or null
 template <int THREADS>
@@ -3223,21 +3214,27 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
     const int W = TILED ? tw : d.W, H = TILED ? th : d.H;
     int n_rooms = d.n_rrooms[e];
     if (n_rooms < 0) n_rooms = 0;
+    // The regions of RenderLds (mwb_lds_layout.h), in its order and stepped by its RL_*_BYTES sizes, but as a pointer chain of this
+    // function's own: with the pointers taken from the struct, the item_res size is folded inside the layout function before early
+    // CSE can share n_strips * 4 with it, and the whole-frame kernels are register-allocated with more SGPR reloads.
+    // The host sizes the launch from RenderLds; that this chain keeps ITS order is checked by nothing but review.
+    static_assert(THREADS == RENDER_THREADS, "RenderLds is laid out for RENDER_THREADS");
     float *rooms = (float *)smem;
-    size_t off = ((size_t)d.R_max * d.room_words * 4 + 15) & ~(size_t)15;
-    float *fc = (float *)(smem + off); off += (size_t)d.frame_words * 4;
-    TexLds *tex = (TexLds *)(smem + off); off += sizeof(TexLds) * d.n_tex;
-    int *cam_room_s = (int *)(smem + off); off += 16 + 2 * (THREADS / WAVE) * sizeof(int);   // + leftover counts
-    uint16_t *queues = (uint16_t *)(smem + off); off += (THREADS / WAVE) * QUEUE_CAP * sizeof(uint16_t);
-    uint32_t *ikeys = (uint32_t *)(smem + off); off += (THREADS / WAVE) * QUEUE_CAP * sizeof(uint32_t);
-    uint16_t *ipix = (uint16_t *)(smem + off); off += (THREADS / WAVE) * QUEUE_CAP * sizeof(uint16_t);
+    size_t off = RL_ROOMS_BYTES(d.R_max, d.room_words);
+    float *fc = (float *)(smem + off); off += RL_FC_BYTES(d.frame_words);
+    TexLds *tex = (TexLds *)(smem + off); off += RL_TEX_BYTES(d.n_tex);
+    int *cam_room_s = (int *)(smem + off); off += RL_SYNC_BYTES;   // + leftover counts
+    uint16_t *queues = (uint16_t *)(smem + off); off += RL_QUEUE_BYTES;
+    uint32_t *ikeys = (uint32_t *)(smem + off); off += RL_IKEYS_BYTES;
+    uint16_t *ipix = (uint16_t *)(smem + off); off += RL_QUEUE_BYTES;
     uint4 *item_res = (uint4 *)(smem + off); off += (size_t)ITEM_RES_BYTES(W);   // per work item: uniform rows + their key
     uint8_t *fb = smem + off;   // the frame is assembled in LDS and leaves as 16-byte coalesced stores
     // entity tasks: a third queue per wave for the 8-sample pixels a mesh may cover, and its leftover counts (behind the frame)
-    uint16_t *mqueues = (uint16_t *)(smem + ((off + (size_t)W * H * 3 + 15) & ~(size_t)15));
-    int *mleft = (int *)(mqueues + (THREADS / WAVE) * MQ_CAP);
-    uint4 *mdesc = (uint4 *)(mleft + 4);   // entity tasks: [MWB_NUM_MESHES], see RenderCtx::mdesc
-    uint8_t *mb_base = (uint8_t *)(mdesc + MWB_NUM_MESHES) + (size_t)(tid / WAVE) * MB_WAVE_BYTES;   // this wave's batch scratch (pixels_mesh)
+    uint8_t *mq_base = smem + RL_BEHIND_FB(off, W, H);
+    uint16_t *mqueues = (uint16_t *)mq_base;
+    int *mleft = (int *)(mq_base + RL_MQUEUE_BYTES);
+    uint4 *mdesc = (uint4 *)(mq_base + RL_MQUEUE_BYTES + RL_MLEFT_BYTES);   // entity tasks: [MWB_NUM_MESHES], see RenderCtx::mdesc
+    uint8_t *mb_base = mq_base + RL_MQUEUE_BYTES + RL_MLEFT_BYTES + RL_MDESC_BYTES + (size_t)(tid / WAVE) * MB_WAVE_BYTES;   // this wave's batch scratch (pixels_mesh)
 
     {   // stage the room table, the frame constants and the texture descriptors
         const int rw = POLY ? MWB_POLY_ROOM_WORDS : MWB_ROOM_WORDS;
@@ -3257,8 +3254,8 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
     RenderCtx<NBOX, POLY> ctx;
     ctx.rooms = rooms; ctx.fc = fc; ctx.tex = tex; ctx.texels = d.texels; ctx.fb = fb;
     ctx.mesh_desc = d.mesh_desc; ctx.mesh_data = d.mesh_data; ctx.mdesc = mdesc;
-    ctx.mb_slots = (unsigned long long *)mb_base; ctx.mb_tasks = (uint16_t *)(mb_base + MB_HALF * WAVE * 8);
-    ctx.mb_pix = (uint32_t *)(mb_base + MB_HALF * WAVE * 8 + MB_TASKS * 2); ctx.mb_count = (int *)(mb_base + MB_HALF * WAVE * 8 + MB_TASKS * 2 + WAVE * 4);
+    ctx.mb_slots = (unsigned long long *)(mb_base + MB_SLOTS_OFF); ctx.mb_tasks = (uint16_t *)(mb_base + MB_PAIRS_OFF);
+    ctx.mb_pix = (uint32_t *)(mb_base + MB_PIX_OFF); ctx.mb_count = (int *)(mb_base + MB_COUNT_OFF);
     ctx.exp_flags = d.exp_flags; ctx.mesh_slots = 0; ctx.dbg_counters = d.dbg_counters;
     if constexpr (NBOX > MWB_MAX_BOXES) {   // which slots hold a mesh in this frame
         uint32_t ms = 0;
@@ -3309,7 +3306,6 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
         ctx.cull_oc[0][0] = uni(fc[FC_CULL_OC]); ctx.cull_oc[0][1] = uni(fc[FC_CULL_OC + 1]); ctx.cull_oc[0][2] = uni(fc[FC_CULL_OC + 2]);
         cull_cc_px[0] = uni(fc[FC_CULL_CC_PIXEL]);
     }
-    (void)cull_cc_px;
     ctx.boxes_in_view = __builtin_amdgcn_readfirstlane(__float_as_int(fc[FC_BOX_IN_VIEW])) != 0;
     ctx.item_res = (d.debug_flags & (1 | 32 | 128)) ? nullptr : item_res;   // filled by the lattice pass below
     ctx.part_h_inv = 65536 / ((H + 3) / 4) + 1;
@@ -3324,12 +3320,12 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
     // time, so that the shading and the 8-sample path always run with dense lanes.
     // the wave index is wave-uniform: in a scalar register, so are the queue addresses derived from it (VGPRs are the budget)
     const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE), lane = tid % WAVE, n_waves = THREADS / WAVE;
-    // queued pixels are packed as (py << wshift) | px (host checks that it fits 16 bits): no integer division
-    const int wshift = 32 - __builtin_clz((unsigned)(W > 1 ? W - 1 : 1));
+    // queued pixels are packed as (py << wshift) | px (the host checks that it fits 16 bits, mwb_pixel_queue_fits): no integer division
+    const int wshift = mwb_coord_bits(W);
     const int wmask = (1 << wshift) - 1;
     // an 8-sample pixel's entry also carries, above the coordinates, how many leading portal crossings its corner rays share
     // (as many bits as 16 - the coordinate bits leave, at most 3; MWB_DEBUG bit 3: none)
-    const int hshift = 32 - __builtin_clz((unsigned)(H > 1 ? H - 1 : 1));
+    const int hshift = mwb_coord_bits(H);
     const int qshift = wshift + hshift, hmask = (1 << hshift) - 1;
     const int skip_max = (d.debug_flags & 8) || qshift >= 16 ? 0 : (1 << (16 - qshift > 3 ? 3 : 16 - qshift)) - 1;
     uint16_t *queue = queues + wave * QUEUE_CAP;
@@ -3922,54 +3918,51 @@ __global__ void intersect_kernel(MwbDev d, int e, int ent, double x, double z, d
 }
 
 // ====================================================================================== launch
-#define RENDER_THREADS 256
-size_t mwb_reset_lds_bytes(const MwbDev &d) {
-    size_t b = (size_t)d.R_max * sizeof(WRoom) + (size_t)d.R_max * sizeof(double) + (size_t)((d.R_max + 3) & ~3) * sizeof(int) + 624 * sizeof(uint32_t);
-    if (d.ent_task) b += (size_t)MWB_MAX_ENTS * (11 * sizeof(double) + 3 * sizeof(int)) + 8 * sizeof(int);   // the entity tasks' slot records
-    if (d.task == MWB_TASK_MAZE) b += (size_t)(d.R_max + 1) / 2 * 13 + 16;   // rows * cols cells: 3 ints + 1 flag each, one frame more
-    return (b + 15) & ~(size_t)15;
+// the render layout (mwb_lds_layout.h) of a handle for a frame or tile of W x H pixels
+static RenderLds render_lds_of(const MwbDev &d, int W, int H) { return render_lds(d.R_max, d.room_words, d.frame_words, d.n_tex, d.ent_task != 0, W, H); }
+size_t mwb_reset_lds_bytes(const MwbDev &d) { return reset_lds(d.R_max, d.ent_task != 0, d.task == MWB_TASK_MAZE).total; }
+size_t mwb_render_lds_bytes(const MwbDev &d) {
+    const bool tiled = d.tile_w > 0;   // observations rendered in tiles (large frames)
+    return render_lds_launch_bytes(render_lds_of(d, tiled ? d.tile_w : d.W, tiled ? d.tile_h : d.H), tiled, d.ent_task != 0, d.debug_flags);
 }
-static size_t render_lds_bytes_for(const MwbDev &d, int W, int H) {
-    size_t b = (((size_t)d.R_max * d.room_words * 4 + 15) & ~(size_t)15) + (size_t)d.frame_words * 4 + sizeof(TexLds) * d.n_tex + 16 + 2 * (RENDER_THREADS / WAVE) * sizeof(int) +
-               (RENDER_THREADS / WAVE) * QUEUE_CAP * (2 * sizeof(uint16_t) + sizeof(uint32_t)) + (size_t)ITEM_RES_BYTES(W) + (size_t)W * H * 3;
-    b = (b + 15) & ~(size_t)15;
-    if (d.ent_task) b += (RENDER_THREADS / WAVE) * MQ_CAP * sizeof(uint16_t) + 16 + 16 * MWB_NUM_MESHES + (RENDER_THREADS / WAVE) * MB_WAVE_BYTES;   // the mesh-pixel queues, their leftover counts, the mesh descriptors, the batch scratch
-    return (b + 15) & ~(size_t)15;
+
+// The one place a handle picks its render instantiation <NBOX, POLY>: f(integral_constant<int, NBOX>, bool_constant<POLY>)
+template <class F>
+static auto with_render_variant(const MwbDev &d, F &&f) {
+    using std::integral_constant;
+    if (d.ent_task) return f(integral_constant<int, MWB_MAX_ENTS>{}, std::false_type{});   // the general entity list: boxes, meshes, frames
+    if (d.poly) return f(integral_constant<int, 1>{}, std::true_type{});                   // YMaze: polygon rooms (one box)
+    if (d.n_boxes == 6) return f(integral_constant<int, 6>{}, std::false_type{});          // PutNext
+    if (d.n_boxes == 2) return f(integral_constant<int, 2>{}, std::false_type{});          // the two-box T-maze, SimToRealPush
+    return f(integral_constant<int, 1>{}, std::false_type{});
 }
+// ... and a run-time render mode its MODE: f(integral_constant<int, MODE>)
+template <class F>
+static auto with_render_mode(int mode, F &&f) {
+    if (mode == 1) return f(std::integral_constant<int, 1>{});
+    if (mode == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 0>{});
+}
+
 // d: the handle's MwbDev with W / H / obs / depth / frame / want_depth / layout set for the view
 #define LIST_GRID 1280   // blocks that walk the compact list of regenerated envs: a handful per step - but ALL of them in the step at
                         // which a whole batch hits the episode limit together (a block with nothing to do exits at once)
 template <int MODE>
 static int launch_tiles(const MwbDev &d, int tile_w, int tile_h, hipStream_t s) {
     const int tiles_x = (d.W + tile_w - 1) / tile_w, tiles_y = (d.H + tile_h - 1) / tile_h;
-    const size_t lds = render_lds_bytes_for(d, tile_w, tile_h);
+    const size_t lds = render_lds_of(d, tile_w, tile_h).total;
     if (lds > 160 * 1024) return -1;
     const size_t blocks = MODE == 1 ? (size_t)(d.N < LIST_GRID ? d.N : LIST_GRID) * tiles_x * tiles_y : (size_t)d.N * tiles_x * tiles_y;
     const dim3 g((unsigned)blocks), b(RENDER_THREADS);
-#define RV(NB, PL)                                                                                                                 \
-    do {                                                                                                                           \
-        if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)render_view_kernel<RENDER_THREADS, MODE, NB, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2; \
-        render_view_kernel<RENDER_THREADS, MODE, NB, PL><<<g, b, lds, s>>>(d, tiles_x, tiles_y, tile_w, tile_h);                   \
-    } while (0)
-    if (d.ent_task) RV(MWB_MAX_ENTS, false);
-    else if (d.poly) RV(1, true);
-    else if (d.n_boxes == 6) RV(6, false);
-    else if (d.n_boxes == 2) RV(2, false);
-    else RV(1, false);
-#undef RV
-    return 0;
+    return with_render_variant(d, [&](auto nbox, auto poly) {
+        const auto kernel = render_view_kernel<RENDER_THREADS, MODE, decltype(nbox)::value, decltype(poly)::value>;
+        if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
+        hipLaunchKernelGGL(kernel, g, b, lds, s, d, tiles_x, tiles_y, tile_w, tile_h);
+        return 0;
+    });
 }
 int mwb_launch_render_view(const MwbDev &d, hipStream_t s) { return launch_tiles<0>(d, VIEW_TILE_W, VIEW_TILE_H, s); }
 void mwb_view_tile(int *w, int *h) { *w = VIEW_TILE_W; *h = VIEW_TILE_H; }
-
-size_t mwb_render_lds_bytes(const MwbDev &d) {
-    if (d.tile_w > 0) return render_lds_bytes_for(d, d.tile_w, d.tile_h);   // observations rendered in tiles (large frames)
-    if (d.ent_task) return render_lds_bytes_for(d, d.W, d.H);
-    size_t b = (((size_t)d.R_max * d.room_words * 4 + 15) & ~(size_t)15) + (size_t)d.frame_words * 4 + sizeof(TexLds) * d.n_tex + 16 + 2 * (RENDER_THREADS / WAVE) * sizeof(int) +
-               (RENDER_THREADS / WAVE) * QUEUE_CAP * (2 * sizeof(uint16_t) + sizeof(uint32_t)) + (size_t)ITEM_RES_BYTES(d.W) + (size_t)d.W * d.H * 3;
-    b += (size_t)(d.debug_flags >> 8) * 128;   // MWB_DEBUG bits 8+: units of 128 B of LDS padding (occupancy experiments)
-    return (b + 15) & ~(size_t)15;
-}
 
 void mwb_launch_step(const MwbDev &d, const int32_t *actions, const uint8_t *skip, hipStream_t s) {
     if (d.ent_task) { hipLaunchKernelGGL(step_ents_kernel, dim3((d.N + 63) / 64), dim3(64), 0, s, d, actions, skip); return; }
@@ -3990,22 +3983,18 @@ int mwb_prepare_kernels(const MwbDev &d) {
     // opt in to more than the default 64 KB of dynamic LDS where a large world needs it (160 KB per CU)
     size_t r = mwb_reset_lds_bytes(d), q = mwb_render_lds_bytes(d);
     if (r > 160 * 1024 || q > 160 * 1024) return -1;
-    {   // the render kernel's pixel queues hold (py << ceil(log2 W)) | px in 16 bits
-        int wshift = 0;
-        const int qw = d.tile_w > 0 ? d.tile_w : d.W, qh = d.tile_w > 0 ? d.tile_h : d.H;
-        while ((1 << wshift) < qw) wshift++;
-        if (((size_t)qh << wshift) > 65536) return -3;
-    }
+    if (!(d.tile_w > 0 ? mwb_pixel_queue_fits(d.tile_w, d.tile_h) : mwb_pixel_queue_fits(d.W, d.H))) return -3;
     if (r > 64 * 1024 && hipFuncSetAttribute((const void *)reset_fn(d.task), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r) != hipSuccess) return -2;
-    if (q > 64 * 1024) {   // large mazes, or any task at a large observation size (the W*H*3 frame is in LDS too)
-        const void *fns[3][3] = {{(const void *)render_kernel<RENDER_THREADS, 0, 1>, (const void *)render_kernel<RENDER_THREADS, 1, 1>, (const void *)render_kernel<RENDER_THREADS, 2, 1>},
-                                 {(const void *)render_kernel<RENDER_THREADS, 0, 2>, (const void *)render_kernel<RENDER_THREADS, 1, 2>, (const void *)render_kernel<RENDER_THREADS, 2, 2>},
-                                 {(const void *)render_kernel<RENDER_THREADS, 0, 6>, (const void *)render_kernel<RENDER_THREADS, 1, 6>, (const void *)render_kernel<RENDER_THREADS, 2, 6>}};
-        const void *pfns[3] = {(const void *)render_kernel<RENDER_THREADS, 0, 1, true>, (const void *)render_kernel<RENDER_THREADS, 1, 1, true>, (const void *)render_kernel<RENDER_THREADS, 2, 1, true>};
-        const void *efns[3] = {(const void *)render_kernel<RENDER_THREADS, 0, MWB_MAX_ENTS>, (const void *)render_kernel<RENDER_THREADS, 1, MWB_MAX_ENTS>, (const void *)render_kernel<RENDER_THREADS, 2, MWB_MAX_ENTS>};
-        for (int m = 0; m < 3; m++)
-            if (hipFuncSetAttribute(d.ent_task ? efns[m] : d.poly ? pfns[m] : fns[d.n_boxes == 6 ? 2 : d.n_boxes == 2 ? 1 : 0][m], hipFuncAttributeMaxDynamicSharedMemorySize, (int)q) != hipSuccess) return -2;
-    }
+    if (q > 64 * 1024)   // large mazes, or any task at a large observation size (the W*H*3 frame is in LDS too)
+        for (int mode = 0; mode < 3; mode++) {
+            const hipError_t err = with_render_variant(d, [&](auto nbox, auto poly) {
+                return with_render_mode(mode, [&](auto m) {
+                    return hipFuncSetAttribute((const void *)render_kernel<RENDER_THREADS, decltype(m)::value, decltype(nbox)::value, decltype(poly)::value>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)q);
+                });
+            });
+            if (err != hipSuccess) return -2;
+        }
     return 0;
 }
 
@@ -4027,42 +4016,18 @@ void mwb_launch_prep(const MwbDev &d, int mode, hipStream_t s) {
     hipLaunchKernelGGL(prep_kernel, dim3(blocks), dim3(256), 0, s, d, mode);
 }
 void mwb_launch_render(const MwbDev &d, int mode, hipStream_t s) {
-    const dim3 g(d.N + d.split_envs), b(RENDER_THREADS);
-    const size_t lds = mwb_render_lds_bytes(d);
-    const dim3 gl(d.N < LIST_GRID ? d.N : LIST_GRID);
-    if (d.tile_w > 0) {   // every frame as a few tiles, one workgroup each (see render_view_kernel): frames too large for one workgroup's LDS
-        if (mode == 1) (void)launch_tiles<1>(d, d.tile_w, d.tile_h, s);
-        else if (mode == 2) (void)launch_tiles<2>(d, d.tile_w, d.tile_h, s);
-        else (void)launch_tiles<0>(d, d.tile_w, d.tile_h, s);
-        return;
-    }
-    if (d.ent_task) {   // the general entity list: boxes, meshes, frames in up to MWB_MAX_ENTS slots
-        if (mode == 1) render_kernel<RENDER_THREADS, 1, MWB_MAX_ENTS><<<gl, b, lds, s>>>(d);
-        else if (mode == 2) render_kernel<RENDER_THREADS, 2, MWB_MAX_ENTS><<<g, b, lds, s>>>(d);
-        else render_kernel<RENDER_THREADS, 0, MWB_MAX_ENTS><<<g, b, lds, s>>>(d);
-        return;
-    }
-    if (d.poly) {   // YMaze: polygon rooms (one box)
-        if (mode == 1) render_kernel<RENDER_THREADS, 1, 1, true><<<gl, b, lds, s>>>(d);
-        else if (mode == 2) render_kernel<RENDER_THREADS, 2, 1, true><<<g, b, lds, s>>>(d);
-        else render_kernel<RENDER_THREADS, 0, 1, true><<<g, b, lds, s>>>(d);
-        return;
-    }
-    if (d.n_boxes == 2) {   // the two-box T-maze: its own instantiation, so that the one-box kernels stay as they are
-        if (mode == 1) render_kernel<RENDER_THREADS, 1, 2><<<gl, b, lds, s>>>(d);
-        else if (mode == 2) render_kernel<RENDER_THREADS, 2, 2><<<g, b, lds, s>>>(d);
-        else render_kernel<RENDER_THREADS, 0, 2><<<g, b, lds, s>>>(d);
-        return;
-    }
-    if (d.n_boxes == 6) {   // PutNext
-        if (mode == 1) render_kernel<RENDER_THREADS, 1, 6><<<gl, b, lds, s>>>(d);
-        else if (mode == 2) render_kernel<RENDER_THREADS, 2, 6><<<g, b, lds, s>>>(d);
-        else render_kernel<RENDER_THREADS, 0, 6><<<g, b, lds, s>>>(d);
-        return;
-    }
-    if (mode == 1) render_kernel<RENDER_THREADS, 1, 1><<<gl, b, lds, s>>>(d);
-    else if (mode == 2) render_kernel<RENDER_THREADS, 2, 1><<<g, b, lds, s>>>(d);
-    else render_kernel<RENDER_THREADS, 0, 1><<<g, b, lds, s>>>(d);
+    with_render_mode(mode, [&](auto m) {
+        constexpr int MODE = decltype(m)::value;
+        if (d.tile_w > 0) {   // every frame as a few tiles, one workgroup each (see render_view_kernel): frames too large for one workgroup's LDS
+            (void)launch_tiles<MODE>(d, d.tile_w, d.tile_h, s);
+            return;
+        }
+        const dim3 g(MODE == 1 ? (d.N < LIST_GRID ? d.N : LIST_GRID) : d.N + d.split_envs), b(RENDER_THREADS);
+        const size_t lds = mwb_render_lds_bytes(d);
+        with_render_variant(d, [&](auto nbox, auto poly) {
+            hipLaunchKernelGGL((render_kernel<RENDER_THREADS, MODE, decltype(nbox)::value, decltype(poly)::value>), g, b, lds, s, d);
+        });
+    });
 }
 // ================================================================================== top view
 // MiniWorldEnv.render_top_view (miniworld.py:1087-1158) for the whole batch: the floorplan from straight above (glOrtho over its

@@ -229,3 +229,29 @@ def test_pair_list_overflow_path_equals_the_list_path(env_id, monkeypatch):
         if t % 5 == 4:
             assert torch.equal(a.obs, b.obs) and torch.equal(a.depth, b.depth), (env_id, t)
     a.close(); b.close()
+
+
+def test_tiled_frames_equal_whole_frames_across_auto_resets(monkeypatch):
+    """MWB_TILE=40x30 renders every frame as four tiles, one workgroup each - the bulk pass (mode 2) and the regenerated envs' side
+    stream (mode 1) included, which no other test reaches for an entity task: observations, depth, reward and done must equal the
+    whole-frame handle's bit for bit after the reset and after every step, through the auto-resets of 5-step episodes"""
+    import torch
+    from gym_miniworld_amd.batch import BatchedMiniWorld
+    n = 4
+    kw = dict(num_envs=n, seed=23, obs_width=80, obs_height=60, want_depth=True, max_episode_steps=5)
+    whole = BatchedMiniWorld("MiniWorld-PickupObjs-v0", **kw)
+    monkeypatch.setenv("MWB_TILE", "40x30")
+    tiled = BatchedMiniWorld("MiniWorld-PickupObjs-v0", **kw)
+    monkeypatch.delenv("MWB_TILE")
+    whole.reset(); tiled.reset()
+    assert torch.equal(whole.obs, tiled.obs) and torch.equal(whole.depth, tiled.depth), "reset"
+    rng = np.random.default_rng(5)
+    n_resets = 0
+    for t in range(12):
+        act = torch.from_numpy(rng.integers(0, 3, n).astype(np.int32))
+        whole.step(act); tiled.step(act)
+        assert torch.equal(whole.obs, tiled.obs) and torch.equal(whole.depth, tiled.depth), t
+        assert torch.equal(whole.reward, tiled.reward) and torch.equal(whole.done, tiled.done), t
+        n_resets += int(whole.done.sum())
+    assert n_resets >= 4
+    whole.close(); tiled.close()
