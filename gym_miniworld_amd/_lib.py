@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("MWB_LIB") or os.path.join(HERE, "libmwbatch.so")   # 
 NPARAM = 13
 STACK_SLIDING = 16   # MWB_STACK_SLIDING
 STACK_FUSED = 32     # MWB_STACK_FUSED
+STACK_GREY = 64      # MWB_STACK_GREY
 STACK_SLACK_FRAMES = 8   # MWB_STACK_SLACK_FRAMES
 ROOM_WORDS = 24
 POLY_ROOM_WORDS = 52   # MWB_TASK_YMAZE (include/miniworld_batch.h)
@@ -65,6 +66,7 @@ EXPORTS = [
     "mwb_get_geometry", "mwb_timing_enable", "mwb_timing_read", "mwb_stack_enable", "mwb_stack_update", "mwb_stack_window", "mwb_check", "mwb_seed_key",
     "mwb_set_task_state", "mwb_set_domain_rand", "mwb_num_textures", "mwb_debug_wg_times", "mwb_set_state", "mwb_num_boxes", "mwb_room_words", "mwb_step_i64", "mwb_render_top_view", "mwb_visible_ents",
     "mwb_set_mesh", "mwb_set_mesh_dims", "mwb_render_view", "mwb_debug_counters", "mwb_frame_reuse_stats",
+    "mwb_grey_enable", "mwb_grey_output", "mwb_grey_convert",
 ]
 
 _lib = None
@@ -121,6 +123,9 @@ def load():
     L.mwb_seed_key.argtypes = [ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32)]
     L.mwb_stack_update.argtypes = [vp, i32, vp]
     L.mwb_stack_window.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.mwb_grey_enable.argtypes = [vp]
+    L.mwb_grey_output.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+    L.mwb_grey_convert.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.mwb_timing_read.argtypes = [vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(i32)]
     if L.mwb_abi_version() != ABI_VERSION:
         raise MwbError("libmwbatch.so ABI version mismatch")

@@ -108,7 +108,7 @@ class BatchedMiniWorld:
 
     def __init__(self, env_id="MiniWorld-OneRoom-v0", num_envs=1, seed=None, domain_rand=False, obs_width=80,
                  obs_height=60, want_depth=False, layout="HWC", device=0, max_episode_steps=None, params=None,
-                 task=None, task_args=None, first_env_index=0, auto_reset=True):
+                 task=None, task_args=None, first_env_index=0, auto_reset=True, greyscale=False):
         import torch
         self.torch = torch
         self.L = _lib.load()
@@ -159,6 +159,9 @@ class BatchedMiniWorld:
         h = ctypes.c_void_p()
         _lib.check(self.L.mwb_create(ctypes.byref(cfg), ctypes.byref(h)))
         self.h = h
+        self.greyscale = bool(greyscale)
+        if self.greyscale:   # before anything renders: the render kernels fill the grey buffer in the pass that writes obs
+            _lib.check(self.L.mwb_grey_enable(self.h))
         self._load_textures()
         if task in TASK_MESHES:
             self._load_meshes(task)
@@ -169,6 +172,13 @@ class BatchedMiniWorld:
         as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, self), device=self.device)  # noqa: E731
         self.obs = as_t(out.obs, obs_shape, "|u1")
         self.depth = as_t(out.depth, (N, H, W, 1), "<f4") if self.want_depth else None
+        # GreyscaleWrapper's observation as float32 (wrappers.py:29-45 + .float()): [N,H,W,1], or [N,1,W,H] transposed; zero-copy
+        self.grey = None
+        if self.greyscale:
+            gp, gb = ctypes.c_void_p(), ctypes.c_size_t()
+            _lib.check(self.L.mwb_grey_output(self.h, ctypes.byref(gp), ctypes.byref(gb)))
+            assert gb.value == N * W * H * 4
+            self.grey = as_t(gp.value, (N, H, W, 1) if layout == "HWC" else (N, 1, W, H), "<f4")
         self.reward = as_t(out.reward, (N,), "<f4")
         self.reward64 = as_t(out.reward64, (N,), "<f8")
         self.done = as_t(out.done, (N,), "|u1")
@@ -327,6 +337,24 @@ class BatchedMiniWorld:
         _lib.check(self.L.mwb_render_view(self.h, out.data_ptr(), dep.data_ptr() if depth else None, W, H, self._stream()))
         return (out, dep) if depth else out
 
+    def grey_convert(self, rgb, layout="HWC"):
+        """GreyscaleWrapper.observation + .float() (wrappers.py:38-45) for any uint8 RGB frames on this device, with the conversion the
+        render kernels use (mwb_grey_convert): [n, H, W, 3] -> float32 [n, H, W, 1] (layout "HWC"), or [n, 3, W, H] -> [n, 1, W, H]
+        ("CWH"); e.g. render_view()'s frames, or the observations of a batch whose frames are rendered in tiles"""
+        torch = self.torch
+        rgb = torch.as_tensor(rgb).to(device=self.device, dtype=torch.uint8).contiguous()
+        if layout == "HWC":
+            n, H, W, c = rgb.shape
+            shape = (n, H, W, 1)
+        else:
+            n, c, W, H = rgb.shape
+            shape = (n, 1, W, H)
+        assert c == 3, "grey_convert: RGB frames"
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        _lib.check(self.L.mwb_grey_convert(self.h, rgb.data_ptr(), out.data_ptr(), int(n), int(W), int(H),
+                                           {"HWC": _lib.LAYOUT_HWC, "CWH": _lib.LAYOUT_CWH}[layout], self._stream()))
+        return out
+
     # ---------------------------------------------------------------------------- introspection
     def check(self):
         """Synchronous: raises if world generation ever flagged a failure (see mwb_check)."""
@@ -446,23 +474,26 @@ class BatchedMiniWorld:
         return rooms[:nr.value], segs[:ns.value]
 
     # ------------------------------------------------------------------------------ frame stack
-    def stack_enable(self, nstack=4, dtype="float32", sliding=True, fused=False):
+    def stack_enable(self, nstack=4, dtype="float32", sliding=True, fused=False, grey=False):
         """Library-owned [N, nstack*3, W, H] stack kept by one fused HIP pass per step
         (VecPyTorchFrameStack + .float(), pytorch-a2c-ppo-acktr/envs.py:117-165). Needs layout='CWH'.
         sliding=True: the stack is a window that moves over a longer run of planes per env, so a step writes the new frame only
         (1/4 of the shifting stack's HBM traffic); stack_update() then returns a strided view [N, nstack*3, W, H] of it (same
         values; a different view object every step).  sliding=False: the shifting stack in one fixed contiguous tensor.
         fused=True (implies sliding): reset() / step() write each new frame into the window themselves, straight from the render
-        kernel's LDS frame, and zero the history of the envs they regenerate - stack_update() then only returns the view."""
+        kernel's LDS frame, and zero the history of the envs they regenerate - stack_update() then only returns the view.
+        grey=True (needs greyscale=True at construction and float32): the stack of the grey frames, [N, nstack, W, H] - one plane
+        per frame (MWB_STACK_GREY); every form above."""
         torch = self.torch
         is_f = {"float32": 1, "uint8": 0}[dtype]
         sliding = sliding or fused
-        _lib.check(self.L.mwb_stack_enable(self.h, int(nstack), is_f | (_lib.STACK_SLIDING if sliding else 0) | (_lib.STACK_FUSED if fused else 0)))
+        _lib.check(self.L.mwb_stack_enable(self.h, int(nstack), is_f | (_lib.STACK_SLIDING if sliding else 0) | (_lib.STACK_FUSED if fused else 0) |
+                                           (_lib.STACK_GREY if grey else 0)))
         out = _lib.MwbOutputs()
         _lib.check(self.L.mwb_get_outputs(self.h, ctypes.byref(out)))
         first, planes = ctypes.c_int32(), ctypes.c_int32()
         _lib.check(self.L.mwb_stack_window(self.h, ctypes.byref(first), ctypes.byref(planes)))
-        self._stack_c, self._stack_sliding = nstack * 3, bool(sliding)
+        self._stack_c, self._stack_sliding = nstack * (1 if grey else 3), bool(sliding)
         shape = (self.num_envs, planes.value, self.W, self.H)
         self._stack_base = torch.as_tensor(_DevView(out.stack, shape, "<f4" if is_f else "|u1", self), device=self.device)
         self.stack = self._stack_base[:, first.value:first.value + self._stack_c]

@@ -68,6 +68,8 @@ struct mwb_handle {
     int stack_n, stack_dtype;
     int stack_fused;               // the render kernels write the frames into the window themselves (MWB_STACK_FUSED)
     int stack_planes, stack_pos;   // sliding-window stack: planes per env (0 = the classic shifting stack), the window's first plane
+    int stack_cpf;                 // channel planes per frame: 3, or 1 (MWB_STACK_GREY: fed from the grey frame)
+    size_t grey_bytes;             // the grey buffer h->dev.grey (mwb_grey_enable), 0 while it is off
     size_t stack_bytes;
     hipStream_t side;
     hipEvent_t ev_fork, ev_join;
@@ -376,6 +378,7 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
     h->view_frame = nullptr;
     h->meshes_dirty = false; h->mesh_data_dev = nullptr; d.mesh_desc = h->mesh_desc_dev; d.mesh_data = nullptr;
     h->stack = nullptr; h->stack_n = 0; h->stack_dtype = 0; h->stack_bytes = 0; h->stack_planes = 0; h->stack_pos = 0; h->stack_fused = 0;
+    h->stack_cpf = 3; d.stk_cpf = 3; h->grey_bytes = 0;
     int prio_lo = 0, prio_hi = 0;
     hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);   // numerically lowest = highest priority
     if (hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, prio_hi) != hipSuccess ||
@@ -638,10 +641,10 @@ static int render_tail(mwb_handle *h, int mode, hipStream_t s) {
 // the history back to the front first when the window has reached the end of its planes.
 static int stack_advance(mwb_handle *h, int after_reset, hipStream_t s) {
     if (!h->stack_fused) return MWB_OK;
-    const int C = h->stack_n * 3, from = h->stack_pos;
-    int pos = after_reset ? 0 : from + 3;
+    const int cpf = h->stack_cpf, C = h->stack_n * cpf, from = h->stack_pos;
+    int pos = after_reset ? 0 : from + cpf;
     if (!after_reset && pos + C > h->stack_planes) {
-        mwb_launch_stack_slide(h->dev, h->stack, h->stack_n, h->stack_planes, h->stack_dtype, 0, from, 3, s);
+        mwb_launch_stack_slide(h->dev, h->stack, h->stack_n, h->stack_planes, h->stack_dtype, 0, from, 3, s, cpf);
         int rc = check_launch("stack_slide_kernel"); if (rc) return rc;
         pos = 0;
     }
@@ -823,33 +826,73 @@ extern "C" int mwb_check(mwb_handle *h) {
     return MWB_OK;
 }
 
+// ---------------------------------------------------------------------------------- greyscale
+extern "C" int mwb_grey_enable(mwb_handle *h) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_grey_enable: null handle");
+    MwbDev &d = h->dev;
+    if (d.grey) return set_err(MWB_ESTATE, "mwb_grey_enable: already enabled");
+    if ((d.W * d.H) % 4) return set_err(MWB_EINVAL, "mwb_grey_enable: W*H must be a multiple of 4");
+    if (d.tile_w > 0) return set_err(MWB_EINVAL, "mwb_grey_enable: not available when observations are rendered in tiles (large frames, MWB_TILE): use mwb_grey_convert");
+    // the buffer is filled by the pass that writes obs: enabled after the first one it would lack the frame already rendered
+    if (h->have_obs) return set_err(MWB_ESTATE, "mwb_grey_enable: must be called before the first mwb_reset / mwb_step / mwb_render");
+    USE_DEVICE(h->cfg.device);
+    float *p = nullptr;
+    const size_t n = (size_t)d.N * d.W * d.H;
+    int rc = dev_alloc(h, &p, n);
+    if (rc) return rc;
+    d.grey = p; h->grey_bytes = n * sizeof(float);
+    return MWB_OK;
+}
+
+extern "C" int mwb_grey_output(mwb_handle *h, float **grey, size_t *bytes) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_grey_output: null handle");
+    if (!h->dev.grey) return set_err(MWB_ESTATE, "mwb_grey_output: call mwb_grey_enable first");
+    if (grey) *grey = h->dev.grey;
+    if (bytes) *bytes = h->grey_bytes;
+    return MWB_OK;
+}
+
+extern "C" int mwb_grey_convert(mwb_handle *h, const uint8_t *rgb_dev, float *grey_dev, int n_frames, int width, int height, int layout, void *stream) {
+    if (!h || !rgb_dev || !grey_dev) return set_err(MWB_EINVAL, "mwb_grey_convert: null argument");
+    if (width < 1 || height < 1 || width > 4096 || height > 4096) return set_err(MWB_EINVAL, "mwb_grey_convert: bad frame size");
+    if (layout != MWB_LAYOUT_HWC && layout != MWB_LAYOUT_CWH) return set_err(MWB_EINVAL, "mwb_grey_convert: bad layout");
+    const long long blocks = (long long)n_frames * ((width * height + 4095) / 4096);
+    if (n_frames < 1 || blocks > 0x7fffffffLL) return set_err(MWB_EINVAL, "mwb_grey_convert: bad frame count");
+    USE_DEVICE(h->cfg.device);
+    mwb_launch_grey_convert(rgb_dev, grey_dev, n_frames, width * height, layout, (hipStream_t)stream);
+    return check_launch("grey_convert_kernel");
+}
+
 // ---------------------------------------------------------------------------------- frame stack
 extern "C" int mwb_stack_enable(mwb_handle *h, int nstack, int dtype) {
     if (!h) return set_err(MWB_EINVAL, "mwb_stack_enable: null handle");
     const MwbDev &d = h->dev;
     const int fused = (dtype & MWB_STACK_FUSED) != 0;
     const int sliding = fused || (dtype & MWB_STACK_SLIDING) != 0;
-    dtype &= ~(MWB_STACK_SLIDING | MWB_STACK_FUSED);
+    const int grey = (dtype & MWB_STACK_GREY) != 0, cpf = grey ? 1 : 3;
+    dtype &= ~(MWB_STACK_SLIDING | MWB_STACK_FUSED | MWB_STACK_GREY);
     if (nstack < 1 || nstack > 16 || (dtype != 0 && dtype != 1)) return set_err(MWB_EINVAL, "mwb_stack_enable: bad nstack / dtype");
     if (d.layout != MWB_LAYOUT_CWH) return set_err(MWB_EINVAL, "mwb_stack_enable: the frame stack is channel-first, create the handle with MWB_LAYOUT_CWH");
     if ((d.W * d.H) % 4) return set_err(MWB_EINVAL, "mwb_stack_enable: W*H must be a multiple of 4");
     if (h->stack) return set_err(MWB_ESTATE, "mwb_stack_enable: already enabled");
+    if (grey && dtype != 1) return set_err(MWB_EINVAL, "mwb_stack_enable: MWB_STACK_GREY needs dtype float32 (the reference defines no uint8 grey)");
+    if (grey && !d.grey) return set_err(MWB_ESTATE, "mwb_stack_enable: MWB_STACK_GREY needs mwb_grey_enable first");
     // a fused window is filled by the render kernels as they produce frames: enabled after the first observation it would
     // lack the current frame until the next pass (the non-fused forms rebuild theirs from the observation buffer)
     if (fused && h->dev.tile_w > 0) return set_err(MWB_EINVAL, "mwb_stack_enable: MWB_STACK_FUSED is not available when observations are rendered in tiles (large frames, MWB_TILE): use MWB_STACK_SLIDING");
     if (fused && h->have_obs) return set_err(MWB_ESTATE, "mwb_stack_enable: MWB_STACK_FUSED must be enabled before the first mwb_reset / mwb_step / mwb_render");
     if (fused && dtype == 0 && (d.W * d.H) % 16) return set_err(MWB_EINVAL, "mwb_stack_enable: a fused uint8 stack needs W*H to be a multiple of 16");
     USE_DEVICE(h->cfg.device);
-    const int planes = sliding ? nstack * 3 + 3 * MWB_STACK_SLACK_FRAMES : nstack * 3;
+    const int planes = sliding ? nstack * cpf + cpf * MWB_STACK_SLACK_FRAMES : nstack * cpf;
     size_t bytes = (size_t)d.N * planes * d.W * d.H * (dtype == 1 ? 4 : 1);
     uint8_t *p = nullptr;
     int rc = dev_alloc(h, &p, bytes);
     if (rc) return rc;
     h->stack = p; h->stack_n = nstack; h->stack_dtype = dtype; h->stack_bytes = bytes;
-    h->stack_planes = sliding ? planes : 0; h->stack_pos = 0; h->stack_fused = fused;
+    h->stack_planes = sliding ? planes : 0; h->stack_pos = 0; h->stack_fused = fused; h->stack_cpf = cpf;
     if (fused) {
         MwbDev &dd = h->dev;
-        dd.stk = p; dd.stk_float = dtype == 1; dd.stk_C = nstack * 3; dd.stk_K = planes; dd.stk_pos = 0;
+        dd.stk = p; dd.stk_float = dtype == 1; dd.stk_C = nstack * cpf; dd.stk_K = planes; dd.stk_pos = 0; dd.stk_cpf = cpf;
     }
     return MWB_OK;
 }
@@ -859,22 +902,22 @@ extern "C" int mwb_stack_update(mwb_handle *h, int after_reset, void *stream) {
     USE_DEVICE(h->cfg.device);
     if (h->stack_fused) return MWB_OK;   // the step / reset that produced the observation has already put it into the window
     if (h->stack_planes) {   // sliding window: the host owns the window position (mwb_stack_window)
-        const int C = h->stack_n * 3, from = h->stack_pos;
-        int mode = 0, pos = from + 3;
+        const int cpf = h->stack_cpf, C = h->stack_n * cpf, from = h->stack_pos;
+        int mode = 0, pos = from + cpf;
         if (after_reset) { mode = 2; pos = 0; }
         else if (pos + C > h->stack_planes) { mode = 1; pos = 0; }
-        mwb_launch_stack_slide(h->dev, h->stack, h->stack_n, h->stack_planes, h->stack_dtype, pos, from, mode, (hipStream_t)stream);
+        mwb_launch_stack_slide(h->dev, h->stack, h->stack_n, h->stack_planes, h->stack_dtype, pos, from, mode, (hipStream_t)stream, cpf);
         h->stack_pos = pos;
         return check_launch("stack_slide_kernel");
     }
-    mwb_launch_stack(h->dev, h->stack, h->stack_n, h->stack_dtype, after_reset, (hipStream_t)stream);
+    mwb_launch_stack(h->dev, h->stack, h->stack_n, h->stack_dtype, after_reset, (hipStream_t)stream, h->stack_cpf);
     return check_launch("stack_kernel");
 }
 
 extern "C" int mwb_stack_window(mwb_handle *h, int *first_plane, int *planes_per_env) {
     if (!h || !h->stack) return set_err(MWB_ESTATE, "mwb_stack_window: call mwb_stack_enable first");
     if (first_plane) *first_plane = h->stack_planes ? h->stack_pos : 0;
-    if (planes_per_env) *planes_per_env = h->stack_planes ? h->stack_planes : h->stack_n * 3;
+    if (planes_per_env) *planes_per_env = h->stack_planes ? h->stack_planes : h->stack_n * h->stack_cpf;
     return MWB_OK;
 }
 

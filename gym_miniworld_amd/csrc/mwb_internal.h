@@ -174,6 +174,7 @@ struct MwbDev {
     float *frame;           // [N][frame_words]
     void *stk;              // fused frame stack (MWB_STACK_FUSED) or null: base of [N][stk_K][W][H] planes, f32 (stk_float) or u8;
     int stk_float, stk_C, stk_K, stk_pos;   // the window the frame being rendered belongs to starts at plane stk_pos
+    int stk_cpf;            // channel planes per frame of that stack: 3, or 1 for a grey stack (MWB_STACK_GREY) fed from the grey frame
     double *world_ext;      // [N][4] min_x max_x min_z max_z of the floorplan (miniworld.py:576-579), written by reset_kernel
     const uint32_t *texels;
     const MwbTexDesc *tex_desc;   // [MWB_MAX_TEX] in device memory
@@ -183,6 +184,7 @@ struct MwbDev {
     double *reward64;
     uint8_t *done;
     int32_t *ep_steps;
+    float *grey;            // greyscale observations (mwb_grey_enable) or null: f32 [N][H][W] (HWC handles) / [N][W][H] (CWH), written with obs
     uint32_t *cost;         // [2N] s_memrealtime ticks (10 ns) the last bulk render spent on env e: whole frame at [2e], or the halves
     uint8_t *bucket;        // [N] scratch of order_kernel
     // blockIdx -> env maps of the bulk render, envs by decreasing measured frame cost (slow frames first), double-buffered
@@ -235,8 +237,11 @@ void mwb_launch_reset(const MwbDev &d, int max_blocks, hipStream_t s);   // grid
 // mode 0: every env; 1: only envs with reset_set; 2: only envs without (lets reset overlap the bulk render)
 void mwb_launch_prep(const MwbDev &d, int mode, hipStream_t s);
 void mwb_launch_render(const MwbDev &d, int mode, hipStream_t s);
-void mwb_launch_stack(const MwbDev &d, void *stack, int nstack, int dtype, int after_reset, hipStream_t s);
-void mwb_launch_stack_slide(const MwbDev &d, void *stack, int nstack, int planes, int dtype, int pos, int from, int mode, hipStream_t s);
+// cpf: channel planes per frame - 3 (fed from d.obs), or 1 (a grey stack, f32 only: fed from d.grey)
+void mwb_launch_stack(const MwbDev &d, void *stack, int nstack, int dtype, int after_reset, hipStream_t s, int cpf = 3);
+void mwb_launch_stack_slide(const MwbDev &d, void *stack, int nstack, int planes, int dtype, int pos, int from, int mode, hipStream_t s, int cpf = 3);
+// RGB frames in device memory -> float32 grey, n_frames x plane pixels (mwb_grey_convert)
+void mwb_launch_grey_convert(const uint8_t *rgb, float *grey, int n_frames, int plane, int layout, hipStream_t s);
 void mwb_launch_intersect(const MwbDev &d, int env, int ent, double x, double z, double radius, int *result_dev, hipStream_t s);
 void mwb_launch_visible(const MwbDev &d, uint32_t *mask_out, hipStream_t s);   // get_visible_ents for every env
 int mwb_launch_render_view(const MwbDev &d, hipStream_t s);   // the agent's view at d.W x d.H in tiles; 0 ok, -1 LDS, -2 HIP

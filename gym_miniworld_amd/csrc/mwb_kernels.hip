@@ -3170,6 +3170,58 @@ __device__ __forceinline__ void stack_put_range(const MwbDev &d, size_t env_base
     }
 }
 
+// GreyscaleWrapper.observation (gym_miniworld/wrappers.py:38-45) followed by the trainer's .float() (pytorch-a2c-ppo-acktr/
+// envs.py:119,128): 0.30 R + 0.59 G + 0.11 B in float64, summed left to right as NumPy does, rounded to float32 once.  In float32
+// alone a third of all colours would round differently; the build's -ffp-contract=off keeps the sum uncontracted.
+__device__ __forceinline__ float grey_of(uint32_t r, uint32_t g, uint32_t b) {
+    return (float)((0.30 * (double)r + 0.59 * (double)g) + 0.11 * (double)b);
+}
+// four pixels whose channels sit in the bytes of r, g and b
+__device__ __forceinline__ float4 grey_of4(uint32_t r, uint32_t g, uint32_t b) {
+    return make_float4(grey_of(r & 255u, g & 255u, b & 255u), grey_of((r >> 8) & 255u, (g >> 8) & 255u, (b >> 8) & 255u),
+                       grey_of((r >> 16) & 255u, (g >> 16) & 255u, (b >> 16) & 255u), grey_of(r >> 24, g >> 24, b >> 24));
+}
+// The pixels [p0, p1) of one RGB frame of `plane` pixels - `src`: the LDS framebuffer, the last-frame cache, or a caller's frame;
+// interleaved (HWC: rows are runs of pixels) or three planes (CWH: columns are) - as grey into dst[p] and, where given, dst2[p]
+// (the newest plane of a grey stack's window).  Four pixels per lane and one 16-byte store where `vec` (plane % 4 == 0, src
+// 4-byte and dst 16-byte aligned) says the frame allows it; the ends of a range that does not start or stop on a multiple of four
+// pixels (the half-frame workgroups': rows of a 42 x 30 frame start at r * 42) go pixel by pixel.  Not inlined: the
+// float64 arithmetic stays out of the register allocation of the frame loop around it.
+template <int THREADS>
+__device__ __noinline__ void grey_put_range(const uint8_t *src, float *dst, float *dst2, int cwh, int plane, int p0, int p1, int vec) {
+    const int tid = threadIdx.x;
+    int a0 = (p0 + 3) & ~3, a1 = p1 & ~3;
+    if (!vec || a0 > a1) { a0 = p1; a1 = p1; }   // no vector part: everything is "head"
+    for (int i = p0 + tid; i < a0; i += THREADS) {
+        const float v = cwh ? grey_of(src[i], src[plane + i], src[2 * plane + i]) : grey_of(src[3 * i], src[3 * i + 1], src[3 * i + 2]);
+        dst[i] = v; if (dst2) dst2[i] = v;
+    }
+    for (int i = a0 / 4 + tid; i < a1 / 4; i += THREADS) {
+        float4 v;
+        if (cwh) {
+            const uint32_t *s1 = (const uint32_t *)src;
+            v = grey_of4(s1[i], s1[plane / 4 + i], s1[plane / 2 + i]);
+        } else {   // 12 bytes: R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+            const uint32_t *s1 = (const uint32_t *)src + 3 * i;
+            const uint32_t w0 = s1[0], w1 = s1[1], w2 = s1[2];
+            v = make_float4(grey_of(w0 & 255u, (w0 >> 8) & 255u, (w0 >> 16) & 255u), grey_of(w0 >> 24, w1 & 255u, (w1 >> 8) & 255u),
+                            grey_of((w1 >> 16) & 255u, w1 >> 24, w2 & 255u), grey_of((w2 >> 8) & 255u, (w2 >> 16) & 255u, w2 >> 24));
+        }
+        ((float4 *)dst)[i] = v; if (dst2) ((float4 *)dst2)[i] = v;
+    }
+    for (int i = a1 + tid; i < p1; i += THREADS) {
+        const float v = cwh ? grey_of(src[i], src[plane + i], src[2 * plane + i]) : grey_of(src[3 * i], src[3 * i + 1], src[3 * i + 2]);
+        dst[i] = v; if (dst2) dst2[i] = v;
+    }
+}
+// where the grey of env e's frame goes: the grey buffer and, with a fused grey stack, the newest plane of the env's window
+template <int THREADS>
+__device__ __forceinline__ void grey_put_env(const MwbDev &d, const int e, const uint8_t *src, int p0, int p1) {
+    const int plane = d.W * d.H;
+    float *newest = (d.stk && d.stk_cpf == 1) ? (float *)d.stk + ((size_t)e * d.stk_K + d.stk_pos + d.stk_C - 1) * plane : nullptr;
+    grey_put_range<THREADS>(src, d.grey + (size_t)e * plane, newest, d.layout == MWB_LAYOUT_CWH, plane, p0, p1, 1);
+}
+
 // The way into the last-frame cache for the frame of a regenerated env (side-stream pass): copied from the outputs its workgroup
 // has just written, after a barrier, by a call that is not inlined - nothing of it is hoisted out of the loop around render_env
 // and kept alive across whole frames (inlined, or stored from LDS inside render_env: 104 - 170 B/lane of scratch, budget 96)
@@ -3182,7 +3234,7 @@ __device__ __noinline__ void keep_frame(uint8_t *frame_keep, const uint8_t *fram
 }
 // The bulk pass' answer for an env whose step changed nothing its frame depends on (d.frame_same): the frame of the step before,
 // from the private cache into the outputs - and into the fused stack's window, as the newest frame - instead of a render.
-template <int THREADS>
+template <int THREADS, bool GREY = false>
 __device__ __forceinline__ void reuse_frame(const MwbDev &d, const int e) {
     const int tid = threadIdx.x;
     const int nbytes = d.W * d.H * 3;
@@ -3192,8 +3244,9 @@ __device__ __forceinline__ void reuse_frame(const MwbDev &d, const int e) {
         const size_t o = (size_t)e * d.W * d.H;
         copy_frame_range<THREADS>((uint8_t *)(d.depth + o), (const uint8_t *)(d.depth_cache + o), 0, d.W * d.H * 4, tid);
     }
-    if (d.stk && d.layout == MWB_LAYOUT_CWH)
+    if (d.stk && d.layout == MWB_LAYOUT_CWH && (!GREY || d.stk_cpf == 3))
         stack_put_range<THREADS>(d, ((size_t)e * d.stk_K + d.stk_pos) * (d.W * d.H), src, 0, nbytes, tid);
+    if constexpr (GREY) { if (d.grey) grey_put_env<THREADS>(d, e, src, 0, d.W * d.H); }   // the cache is RGB: the grey frame is computed from it again
 }
 
 // Renders one env with the whole workgroup (called once per workgroup, or per list entry on the side stream).
@@ -3204,7 +3257,7 @@ __device__ __forceinline__ void reuse_frame(const MwbDev &d, const int e) {
 // reference's 800 x 600 human view, or any observation size whose frame does not fit LDS): everything below works in tile-local
 // pixel coordinates; only the camera's window mapping carries the offset - (2 (wx + ox) - W) / W = (2 wx - (W - 2 ox)) / W, exact
 // in float32 - and the tile's rows go to their places in the big frame.
-template <int THREADS, int NBOX, bool LOOPED, bool POLY, bool TILED = false>
+template <int THREADS, int NBOX, bool LOOPED, bool POLY, bool TILED = false, bool GREY = false>
 __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const int part, unsigned char *smem, const int tx0 = 0,
                                            const int ty0 = 0, const int tw = 0, const int th = 0) {
     // LOOPED (the body sits in a loop over the regenerated-env list): make the lane id opaque to the optimiser so that
@@ -3698,17 +3751,30 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
         // regenerated in this pass gets its history planes zeroed (VecPyTorchFrameStack, envs.py:149-156): no stack pass.
         if (d.stk && d.layout == MWB_LAYOUT_CWH) {
             const int plane = W * H, C = d.stk_C;
+            const int cpf = GREY ? d.stk_cpf : 3;   // planes per frame: a grey stack (1) exists only behind the GREY instantiations
             const size_t env_base = ((size_t)e * d.stk_K + d.stk_pos) * plane;   // first element of the window
             int xa = 0, xb = W;
             if (part >= 0) { const int midx = half_strips * (TILE_CX - 1) < W ? half_strips * (TILE_CX - 1) : W; xa = part ? midx : 0; xb = part ? W : midx; }
             if (LOOPED || d.reset_set[e]) {   // regenerated env (side-stream list, or a pass that regenerates in place; never the bulk pass)
-                const int n4 = (C - 3) * plane / 4;   // a half-frame workgroup zeroes half of the history
+                const int n4 = (C - cpf) * plane / 4;   // a half-frame workgroup zeroes half of the history
                 const int i0 = part < 0 ? 0 : (part ? n4 / 2 : 0), i1 = part < 0 ? n4 : (part ? n4 : n4 / 2);
                 if (d.stk_float) { float4 *z = (float4 *)((float *)d.stk + env_base); for (int i = i0 + tid; i < i1; i += THREADS) z[i] = make_float4(0, 0, 0, 0); }
                 else { uint32_t *z = (uint32_t *)((uint8_t *)d.stk + env_base); for (int i = i0 + tid; i < i1; i += THREADS) z[i] = 0u; }
             }
+            if (cpf == 3)   // (a grey stack's newest plane is written with the grey frame, below)
             for (int q = 0; q < 3; q++)   // byte range of this channel plane's columns in fb (multiples of 4: W*H % 4 == 0 checked, H*15 ... see host check)
                 stack_put_range<THREADS>(d, env_base, fb, (q * W + xa) * H, (q * W + xb) * H, tid);
+        }
+        // Greyscale observations (mwb_grey_enable; the GREY instantiations = render_grey_kernel): the pixels this workgroup has just
+        // copied out, as grey, from the same LDS frame - rows for HWC frames, columns for CWH ones, both one run of pixels - and with
+        // a grey stack (stk_cpf == 1) into its window's newest plane as well
+        if constexpr (GREY && !TILED) {
+            if (d.grey) {
+                int p0 = 0, p1 = W * H;
+                if (part >= 0 && !split_x) { const int mid = 2 * part_h < H ? 2 * part_h : H; p0 = part ? mid * W : 0; p1 = part ? H * W : mid * W; }
+                else if (part >= 0) { const int midx = half_strips * (TILE_CX - 1) < W ? half_strips * (TILE_CX - 1) : W; p0 = part ? midx * H : 0; p1 = part ? W * H : midx * H; }
+                grey_put_env<THREADS>(d, e, fb, p0, p1);
+            }
         }
     }
 }
@@ -3717,14 +3783,13 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
 // 2: all the others (bulk).  A template parameter so that the three launches carry distinct kernel names
 // in profiles.
 // NBOX = MWB_MAX_ENTS: the entity tasks' instantiation (mesh BVH walks, frames): 4 workgroups per CU (128 VGPRs) instead of 5
-template <int THREADS, int MODE, int NBOX, bool POLY = false>
-__global__ void __launch_bounds__(THREADS, NBOX > MWB_MAX_BOXES ? ENT_WGS_PER_CU : 5) render_kernel(MwbDev d) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+template <int THREADS, int MODE, int NBOX, bool POLY, bool GREY>
+__device__ __forceinline__ void render_body(const MwbDev &d, unsigned char *smem) {
     if (MODE == 1) {
         __builtin_amdgcn_s_setprio(3);   // the few regenerated envs, beside the bulk render (see reset_kernel)
         const int count = d.reset_count[0];
         for (int li = blockIdx.x; li < count; li += gridDim.x) {
-            render_env<THREADS, NBOX, true, POLY>(d, d.reset_list[li], -1, smem);
+            render_env<THREADS, NBOX, true, POLY, false, GREY>(d, d.reset_list[li], -1, smem);
             __syncthreads();   // LDS is reused by the next env of this block
             if (d.frame_cache) {
                 const size_t e = (size_t)d.reset_list[li], px = (size_t)d.W * d.H;
@@ -3746,13 +3811,13 @@ __global__ void __launch_bounds__(THREADS, NBOX > MWB_MAX_BOXES ? ENT_WGS_PER_CU
         if (MODE == 2 && d.reset_set[e]) return;   // block-uniform
         if (d.reuse_pass && d.frame_same && d.frame_same[e]) {   // block-uniform; decided by this step's step kernel (never for a regenerated env)
             if (part <= 0) {   // of a half-frame pair the first copies the frame, the second has nothing to do
-                reuse_frame<THREADS>(d, e);
+                reuse_frame<THREADS, GREY>(d, e);
                 if (threadIdx.x == 0) atomicAdd(d.reuse_stats, 1ull);
             }
             return;   // d.cost[e] keeps the last measured cost: order_kernel does not file the env under "cheapest"
         }
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();   // read by every wave: stays in scalar registers
-        render_env<THREADS, NBOX, false, POLY>(d, e, part, smem);
+        render_env<THREADS, NBOX, false, POLY, false, GREY>(d, e, part, smem);
         if (threadIdx.x == 0) {
             const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
             if (d.wg_ts) { d.wg_ts[2 * b] = t0; d.wg_ts[2 * b + 1] = t1; }
@@ -3762,6 +3827,20 @@ __global__ void __launch_bounds__(THREADS, NBOX > MWB_MAX_BOXES ? ENT_WGS_PER_CU
             if (d.reuse_pass && part <= 0) atomicAdd(d.reuse_stats + 1, 1ull);   // here, not ahead of the frame: there it cost 136 B/lane of spills
         }
     }
+}
+template <int THREADS, int MODE, int NBOX, bool POLY = false>
+__global__ void __launch_bounds__(THREADS, NBOX > MWB_MAX_BOXES ? ENT_WGS_PER_CU : 5) render_kernel(MwbDev d) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    render_body<THREADS, MODE, NBOX, POLY, false>(d, smem);
+}
+// The same with greyscale observations (mwb_grey_enable): the copy-out also writes each frame as float32 grey.  A kernel of its own
+// and not a branch on d.grey in render_kernel: measured there, the branch (a call to grey_put_range in the copy-out, registers and
+// scratch unchanged) cost the RGB path 5 % on maze8192 (profiles/grey_stack_ab.json); this way handles without grey run the
+// kernels they ran before, instruction for instruction.
+template <int THREADS, int MODE, int NBOX, bool POLY = false>
+__global__ void __launch_bounds__(THREADS, NBOX > MWB_MAX_BOXES ? ENT_WGS_PER_CU : 5) render_grey_kernel(MwbDev d) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    render_body<THREADS, MODE, NBOX, POLY, true>(d, smem);
 }
 
 // The agent's view at any size (mwb_render_view): a grid of tiles per env, one workgroup each.  d.W x d.H is the view's size, d.obs /
@@ -3795,24 +3874,13 @@ __global__ void __launch_bounds__(THREADS, NBOX > MWB_MAX_BOXES ? ENT_WGS_PER_CU
     render_env<THREADS, NBOX, false, POLY, true>(d, e, -1, smem, tx0, ty0, tw, th);
 }
 
-// ================================================================================== frame stack
-// VecPyTorchFrameStack.step_wait / reset (pytorch-a2c-ppo-acktr/envs.py:149-162) fused with VecPyTorch's
-// uint8 -> float conversion (envs.py:128): one streaming pass, 16 bytes per lane.  HBM-bound: per env it
-// reads (C-3) planes + the new observation and writes C planes.
+// the newest frame of env e into the planes [first, first + cpf) of its stack: the three channel planes of the observation (u8 ->
+// f32 where the stack is float), or - cpf 1, a grey stack (MWB_STACK_GREY, f32 only) - the grey frame, which is float already
 template <typename V, bool IS_FLOAT>
-__global__ void __launch_bounds__(256) stack_kernel(MwbDev d, V *__restrict__ stack, int C, int after_reset) {
-    const int e = blockIdx.y;
-    const int plane4 = (d.W * d.H) / 4;   // vectors of 4 pixels per channel plane
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= plane4) return;
-    V *base = stack + (size_t)e * C * plane4;
-    const bool clear = after_reset || d.done[e];
-    V zero;
-    memset(&zero, 0, sizeof(V));
-    for (int c = 0; c < C - 3; c++) {
-        V v = zero;
-        if (!clear) v = base[(size_t)(c + 3) * plane4 + j];
-        base[(size_t)c * plane4 + j] = v;
+__device__ __forceinline__ void stack_newest(const MwbDev &d, V *__restrict__ base, int e, int first, int cpf, int plane4, int j) {
+    if (cpf == 1) {
+        if constexpr (IS_FLOAT) base[(size_t)first * plane4 + j] = ((const float4 *)(d.grey + (size_t)e * d.W * d.H))[j];
+        return;
     }
     const uint32_t *obs = (const uint32_t *)(d.obs + (size_t)e * 3 * d.W * d.H);   // CWH: [3][W][H]
 #pragma unroll
@@ -3824,17 +3892,38 @@ __global__ void __launch_bounds__(256) stack_kernel(MwbDev d, V *__restrict__ st
         } else {
             v = p;
         }
-        base[(size_t)(C - 3 + k) * plane4 + j] = v;
+        base[(size_t)(first + k) * plane4 + j] = v;
     }
 }
 
-// The same stack as a SLIDING WINDOW over K > C channel planes per env: the view of step t is planes [pos, pos + C); a step
-// moves the window three planes on and writes only the new frame (3 planes) - the C - 3 planes of history stay where they
-// are - and zeroes the history of the envs whose episode ended; when the window reaches the end of the K planes the
-// history is copied back to the front (the classic pass, once every (K - C) / 3 + 1 steps).  mode: 0 slide to `pos` (the
-// window's new first plane), 1 wrap (history from `from`, window at 0), 2 after reset (window at 0, history zeroed).
+// VecPyTorchFrameStack.step_wait / reset (pytorch-a2c-ppo-acktr/envs.py:149-162) fused with VecPyTorch's
+// uint8 -> float conversion (envs.py:128): one streaming pass, 16 bytes per lane.  HBM-bound: per env it
+// reads (C-3) planes + the new observation and writes C planes.
 template <typename V, bool IS_FLOAT>
-__global__ void __launch_bounds__(256) stack_slide_kernel(MwbDev d, V *__restrict__ stack, int C, int K, int pos, int from, int mode) {
+__global__ void __launch_bounds__(256) stack_kernel(MwbDev d, V *__restrict__ stack, int C, int cpf, int after_reset) {
+    const int e = blockIdx.y;
+    const int plane4 = (d.W * d.H) / 4;   // vectors of 4 pixels per channel plane
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= plane4) return;
+    V *base = stack + (size_t)e * C * plane4;
+    const bool clear = after_reset || d.done[e];
+    V zero;
+    memset(&zero, 0, sizeof(V));
+    for (int c = 0; c < C - cpf; c++) {
+        V v = zero;
+        if (!clear) v = base[(size_t)(c + cpf) * plane4 + j];
+        base[(size_t)c * plane4 + j] = v;
+    }
+    stack_newest<V, IS_FLOAT>(d, base, e, C - cpf, cpf, plane4, j);
+}
+
+// The same stack as a SLIDING WINDOW over K > C channel planes per env: the view of step t is planes [pos, pos + C); a step
+// moves the window one frame (cpf planes: three, or one of a grey stack) on and writes only the new frame - the C - cpf planes of
+// history stay where they are - and zeroes the history of the envs whose episode ended; when the window reaches the end of the K
+// planes the history is copied back to the front (the classic pass, once every (K - C) / cpf + 1 steps).  mode: 0 slide to `pos`
+// (the window's new first plane), 1 wrap (history from `from`, window at 0), 2 after reset (window at 0, history zeroed).
+template <typename V, bool IS_FLOAT>
+__global__ void __launch_bounds__(256) stack_slide_kernel(MwbDev d, V *__restrict__ stack, int C, int cpf, int K, int pos, int from, int mode) {
     const int e = blockIdx.y;
     const int plane4 = (d.W * d.H) / 4;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3844,39 +3933,42 @@ __global__ void __launch_bounds__(256) stack_slide_kernel(MwbDev d, V *__restric
     V zero;
     memset(&zero, 0, sizeof(V));
     if (mode == 3) {   // fused stack: the history back to the front, nothing else (the render kernels write frames and zero finished envs)
-        for (int c = 0; c < C - 3; c++) base[(size_t)c * plane4 + j] = base[(size_t)(from + 3 + c) * plane4 + j];
+        for (int c = 0; c < C - cpf; c++) base[(size_t)c * plane4 + j] = base[(size_t)(from + cpf + c) * plane4 + j];
         return;
     }
     if (mode == 1 && !clear) {
-        for (int c = 0; c < C - 3; c++) base[(size_t)c * plane4 + j] = base[(size_t)(from + 3 + c) * plane4 + j];
+        for (int c = 0; c < C - cpf; c++) base[(size_t)c * plane4 + j] = base[(size_t)(from + cpf + c) * plane4 + j];
     } else if (clear) {
-        for (int c = 0; c < C - 3; c++) base[(size_t)(pos + c) * plane4 + j] = zero;
+        for (int c = 0; c < C - cpf; c++) base[(size_t)(pos + c) * plane4 + j] = zero;
     }
-    const uint32_t *obs = (const uint32_t *)(d.obs + (size_t)e * 3 * d.W * d.H);   // CWH: [3][W][H]
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        uint32_t p = obs[(size_t)k * plane4 + j];
-        V v;
-        if constexpr (IS_FLOAT) {
-            v.x = (float)(p & 255u); v.y = (float)((p >> 8) & 255u); v.z = (float)((p >> 16) & 255u); v.w = (float)(p >> 24);
-        } else {
-            v = p;
-        }
-        base[(size_t)(pos + C - 3 + k) * plane4 + j] = v;
-    }
+    stack_newest<V, IS_FLOAT>(d, base, e, pos + C - cpf, cpf, plane4, j);
 }
-void mwb_launch_stack_slide(const MwbDev &d, void *stack, int nstack, int planes, int dtype, int pos, int from, int mode, hipStream_t s) {
+void mwb_launch_stack_slide(const MwbDev &d, void *stack, int nstack, int planes, int dtype, int pos, int from, int mode, hipStream_t s, int cpf) {
     const int plane4 = (d.W * d.H) / 4;
     dim3 grid((plane4 + 255) / 256, d.N);
-    if (dtype == 1) stack_slide_kernel<float4, true><<<grid, dim3(256), 0, s>>>(d, (float4 *)stack, nstack * 3, planes, pos, from, mode);
-    else stack_slide_kernel<uint32_t, false><<<grid, dim3(256), 0, s>>>(d, (uint32_t *)stack, nstack * 3, planes, pos, from, mode);
+    if (dtype == 1) stack_slide_kernel<float4, true><<<grid, dim3(256), 0, s>>>(d, (float4 *)stack, nstack * cpf, cpf, planes, pos, from, mode);
+    else stack_slide_kernel<uint32_t, false><<<grid, dim3(256), 0, s>>>(d, (uint32_t *)stack, nstack * cpf, cpf, planes, pos, from, mode);
 }
 
-void mwb_launch_stack(const MwbDev &d, void *stack, int nstack, int dtype, int after_reset, hipStream_t s) {
+void mwb_launch_stack(const MwbDev &d, void *stack, int nstack, int dtype, int after_reset, hipStream_t s, int cpf) {
     const int plane4 = (d.W * d.H) / 4;
     dim3 grid((plane4 + 255) / 256, d.N);
-    if (dtype == 1) stack_kernel<float4, true><<<grid, dim3(256), 0, s>>>(d, (float4 *)stack, nstack * 3, after_reset);
-    else stack_kernel<uint32_t, false><<<grid, dim3(256), 0, s>>>(d, (uint32_t *)stack, nstack * 3, after_reset);
+    if (dtype == 1) stack_kernel<float4, true><<<grid, dim3(256), 0, s>>>(d, (float4 *)stack, nstack * cpf, cpf, after_reset);
+    else stack_kernel<uint32_t, false><<<grid, dim3(256), 0, s>>>(d, (uint32_t *)stack, nstack * cpf, cpf, after_reset);
+}
+
+// mwb_grey_convert: any RGB frames in device memory through grey_put_range, the render kernels' own way out to grey - a block
+// takes GREY_CONVERT_RUN pixels of one frame
+#define GREY_CONVERT_RUN 4096
+__global__ void __launch_bounds__(256) grey_convert_kernel(const uint8_t *__restrict__ rgb, float *__restrict__ grey, int runs_per_frame, int plane, int cwh, int vec) {
+    const int f = blockIdx.x / runs_per_frame, run = blockIdx.x - f * runs_per_frame;
+    const int p0 = run * GREY_CONVERT_RUN, p1 = plane - p0 < GREY_CONVERT_RUN ? plane : p0 + GREY_CONVERT_RUN;
+    grey_put_range<256>(rgb + (size_t)f * plane * 3, grey + (size_t)f * plane, nullptr, cwh, plane, p0, p1, vec);
+}
+void mwb_launch_grey_convert(const uint8_t *rgb, float *grey, int n_frames, int plane, int layout, hipStream_t s) {
+    const int runs = (plane + GREY_CONVERT_RUN - 1) / GREY_CONVERT_RUN;
+    const int vec = plane % 4 == 0 && ((uintptr_t)rgb & 3) == 0 && ((uintptr_t)grey & 15) == 0;
+    grey_convert_kernel<<<dim3((unsigned)n_frames * (unsigned)runs), dim3(256), 0, s>>>(rgb, grey, runs, plane, layout == MWB_LAYOUT_CWH, vec);
 }
 
 // ============================================================================== small utilities
@@ -3989,7 +4081,10 @@ int mwb_prepare_kernels(const MwbDev &d) {
         for (int mode = 0; mode < 3; mode++) {
             const hipError_t err = with_render_variant(d, [&](auto nbox, auto poly) {
                 return with_render_mode(mode, [&](auto m) {
-                    return hipFuncSetAttribute((const void *)render_kernel<RENDER_THREADS, decltype(m)::value, decltype(nbox)::value, decltype(poly)::value>,
+                    const hipError_t e0 = hipFuncSetAttribute((const void *)render_kernel<RENDER_THREADS, decltype(m)::value, decltype(nbox)::value, decltype(poly)::value>,
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)q);
+                    if (e0 != hipSuccess) return e0;   // (greyscale is enabled after creation: both kernels are made ready)
+                    return hipFuncSetAttribute((const void *)render_grey_kernel<RENDER_THREADS, decltype(m)::value, decltype(nbox)::value, decltype(poly)::value>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)q);
                 });
             });
@@ -4025,7 +4120,8 @@ void mwb_launch_render(const MwbDev &d, int mode, hipStream_t s) {
         const dim3 g(MODE == 1 ? (d.N < LIST_GRID ? d.N : LIST_GRID) : d.N + d.split_envs), b(RENDER_THREADS);
         const size_t lds = mwb_render_lds_bytes(d);
         with_render_variant(d, [&](auto nbox, auto poly) {
-            hipLaunchKernelGGL((render_kernel<RENDER_THREADS, MODE, decltype(nbox)::value, decltype(poly)::value>), g, b, lds, s, d);
+            if (d.grey) hipLaunchKernelGGL((render_grey_kernel<RENDER_THREADS, MODE, decltype(nbox)::value, decltype(poly)::value>), g, b, lds, s, d);
+            else hipLaunchKernelGGL((render_kernel<RENDER_THREADS, MODE, decltype(nbox)::value, decltype(poly)::value>), g, b, lds, s, d);
         });
     });
 }

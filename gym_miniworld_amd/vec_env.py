@@ -115,6 +115,11 @@ class MiniWorldVecEnv(VecEnv):
     transpose=True  -> observations are (3, W, H) like TransposeImage (envs.py:96-107)
     to_float=True   -> float32 0..255 device tensor like VecPyTorch (envs.py:117-130); False keeps uint8
     frame_stack=k   -> [N, k*3, W, H] ring like VecPyTorchFrameStack (envs.py:135-165), zeroed on done
+    greyscale=True  -> GreyscaleWrapper's observations (gym_miniworld/wrappers.py:29-45) as the float32 the trainer makes of them:
+                       (1, W, H) - (H, W, 1) untransposed - and (k, W, H) with frame_stack=k, written by the render
+                       kernels themselves (needs to_float=True: the reference defines no uint8 grey).  Without frame_stack the
+                       observation returned IS the library's grey buffer (no copy, unlike the RGB path's obs.float()): the next
+                       step overwrites it, so a caller that keeps observations by reference must clone them
     torch_api=True  -> actions arrive as LongTensor [N,1], rewards leave as CPU FloatTensor [N,1]
                        (VecPyTorch); False -> numpy in / numpy out like SubprocVecEnv
     feature_info    -> every info dict carries "feature" (length-2 zeros) as the fork's PPO loop
@@ -130,15 +135,18 @@ class MiniWorldVecEnv(VecEnv):
     """
 
     def __init__(self, env_id, num_envs, seed=1, device=0, domain_rand=False, transpose=True, to_float=True,
-                 frame_stack=0, torch_api=True, feature_info=False, first_env_index=0, graph=False, **kwargs):
+                 frame_stack=0, torch_api=True, feature_info=False, first_env_index=0, graph=False, greyscale=False, **kwargs):
         import torch
         from .batch import BatchedMiniWorld
         from . import _lib
         self.torch = torch
+        self.greyscale = bool(greyscale)
+        assert to_float or not self.greyscale, "greyscale observations are float32 (GreyscaleWrapper + .float()): to_float=True"
         self.batch = BatchedMiniWorld(env_id, num_envs=num_envs, seed=seed, domain_rand=domain_rand, device=device,
-                                      layout="CWH" if transpose else "HWC", first_env_index=first_env_index, **kwargs)
+                                      layout="CWH" if transpose else "HWC", first_env_index=first_env_index, greyscale=self.greyscale, **kwargs)
         b = self.batch
-        shape = (3, b.W, b.H) if transpose else (b.H, b.W, 3)
+        nch = 1 if self.greyscale else 3
+        shape = (nch, b.W, b.H) if transpose else (b.H, b.W, nch)
         self.to_float, self.torch_api, self.nstack = to_float, torch_api, int(frame_stack)
         self.shape_dim0 = shape[0]
         if self.nstack:
@@ -149,9 +157,9 @@ class MiniWorldVecEnv(VecEnv):
             # graph would freeze the host-side window position: the shifting stack there)
             fuse = not graph and (to_float or (b.W * b.H) % 16 == 0)
             try:
-                self.stackedobs = b.stack_enable(self.nstack, "float32" if to_float else "uint8", sliding=not graph, fused=fuse)
+                self.stackedobs = b.stack_enable(self.nstack, "float32" if to_float else "uint8", sliding=not graph, fused=fuse, grey=self.greyscale)
             except _lib.MwbError:
-                if not fuse:
+                if not fuse or self.greyscale:   # (no grey frames from a batch rendered in tiles: the constructor has refused already)
                     raise
                 # observations rendered in tiles (frames too large for one workgroup's LDS, MWB_TILE): the sliding window, one pass
                 self.stackedobs = b.stack_enable(self.nstack, "float32" if to_float else "uint8", sliding=not graph, fused=False)
@@ -188,6 +196,8 @@ class MiniWorldVecEnv(VecEnv):
     def _obs_out(self, done=None):
         if self.nstack:   # VecPyTorchFrameStack.reset / step_wait, envs.py:149-162
             return self.batch.stack_update(after_reset=done is None)
+        if self.greyscale:   # float32 already; the library's buffer, valid until the next step (as the stacked observations are)
+            return self.batch.grey
         obs = self.batch.obs
         return obs.float() if self.to_float else obs   # torch.from_numpy(obs).float().to(device), envs.py:119,128
 

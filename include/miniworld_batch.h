@@ -285,8 +285,38 @@ int mwb_stack_enable(mwb_handle *h, int nstack, int dtype);
  * A view of an earlier window position is guaranteed only until the next pass: the history planes of an env that ends are
  * zeroed in place; for envs that keep running it stays intact for MWB_STACK_SLACK_FRAMES + 1 - nstack further steps. */
 #define MWB_STACK_FUSED 32
+/* dtype | MWB_STACK_GREY: the stack of GreyscaleWrapper's frames (below) - nstack planes per env instead of nstack*3, [N, nstack,
+ * W, H], each step's grey frame in the newest ONE plane.  Needs mwb_grey_enable first (MWB_ESTATE otherwise) and dtype 1
+ * (MWB_EINVAL with u8: the reference defines no uint8 grey).  Combines with the shifting stack, MWB_STACK_SLIDING and
+ * MWB_STACK_FUSED: in the sliding forms the window moves one plane per step over nstack + MWB_STACK_SLACK_FRAMES planes
+ * (mwb_stack_window reports them); the partial-reset rule and the history guarantee above hold with "three planes" read as "one
+ * plane".  The non-fused forms take their frames from the grey buffer in mwb_stack_update; the fused one is written by the render kernels,
+ * together with the grey buffer. */
+#define MWB_STACK_GREY 64
 int mwb_stack_window(mwb_handle *h, int *first_plane, int *planes_per_env);
 int mwb_stack_update(mwb_handle *h, int after_reset, void *stream);
+
+/* ---- greyscale observations ------------------------------------------------------------------ */
+/* replaces: GreyscaleWrapper (gym_miniworld/wrappers.py:29-45) followed by VecPyTorch's .float() (pytorch-a2c-ppo-acktr/
+ * envs.py:119,128): grey = float32((0.30 R + 0.59 G) + 0.11 B), the sum in float64 as NumPy evaluates it, rounded once - bit for
+ * bit the reference's values.  Allocates a library-owned float32 buffer, [N][H][W] for MWB_LAYOUT_HWC handles (read it as
+ * [N,H,W,1], the wrapper's observation_space) and [N][W][H] for MWB_LAYOUT_CWH ones ([N,1,W,H], after TransposeImage); every
+ * mwb_reset / mwb_step / mwb_render from then on fills it in the pass that writes `obs`: the render kernel's copy-out writes each
+ * frame twice, as RGB bytes and as grey, from the same LDS frame (handles with grey run the render_grey_kernel instantiations,
+ * handles without it the kernels they always ran).  obs, depth and every other output are what they are without it.  Must be called before the first mwb_reset / mwb_step / mwb_render (MWB_ESTATE
+ * otherwise: the buffer would lack the frame already rendered); MWB_EINVAL when W*H is no multiple of 4 or observations are
+ * rendered in tiles (large frames, MWB_TILE: convert those with mwb_grey_convert); MWB_ESTATE when already enabled.  There is
+ * no uint8 grey: the reference defines none. */
+int mwb_grey_enable(mwb_handle *h);
+/* the buffer mwb_grey_enable allocated and its size in bytes (either pointer may be NULL); MWB_ESTATE before mwb_grey_enable.
+ * replaces: reading the observation GreyscaleWrapper.observation returned (wrappers.py:38-45) */
+int mwb_grey_output(mwb_handle *h, float **grey, size_t *bytes);
+/* replaces: GreyscaleWrapper.observation (wrappers.py:38-45) + .float() applied to ANY frames: n_frames RGB frames of width x
+ * height in device memory - MWB_LAYOUT_HWC: interleaved [n][height][width][3], MWB_LAYOUT_CWH: three planes [n][3][width][height]
+ * - to float32 [n][height][width] / [n][width][height], with the conversion the render kernels use; e.g. mwb_render_view's
+ * output, or the observations of a handle whose frames are rendered in tiles.  Any size up to 4096 x 4096; enqueued on `stream`. */
+int mwb_grey_convert(mwb_handle *h, const uint8_t *rgb_dev, float *grey_dev, int n_frames, int width, int height, int layout,
+                     void *stream);
 
 /* World generation cannot fail for the four tasks with sane arguments; if it ever does (a portal outside
  * its wall, more than one portal on an edge, a placement that finds no free spot in 100000 draws - the
