@@ -6,7 +6,7 @@ stably sorted by material name, float32 vertex arrays [F, 3, *], the re-centring
 reference's own extents (`max_coords = verts.max(axis=0).min(axis=0)` for the centring - objmesh.py:164 - and the true
 maximum for `max_coords` afterwards, objmesh.py:175), per-face `Kd` colour (white without a material), the default
 texture `<mesh>.png` when it exists (objmesh.py:227-231).  tests/golden/meshes.json holds SHA-256 digests of the arrays the
-unmodified reference builds; tests/test_meshes.py requires equality.
+unmodified reference builds; the entity tasks' CPU state test under tests/ (its mesh digest check) requires equality.
 
 The six colour variants `ball_<c>.obj` / `key_<c>.obj` of the reference are byte-identical copies of `ball.obj` / `key.obj`
 that differ in their `.mtl` only, so one geometry file per shape is shipped.
