@@ -28,6 +28,7 @@ MAX_ENTS = 20            # MWB_MAX_ENTS
 MESH_GEOMS = ["ball", "key", "medkit", "duckie", "building", "cone"]   # MWB_MESH_*
 TEX_MESH0, TEX_CHAR0 = 21, 25
 LAYOUT_HWC, LAYOUT_CWH = 0, 1
+COPY_NO_RENDER = 1   # MWB_COPY_NO_RENDER
 
 
 class MwbConfig(ctypes.Structure):
@@ -67,6 +68,7 @@ EXPORTS = [
     "mwb_set_task_state", "mwb_set_domain_rand", "mwb_num_textures", "mwb_debug_wg_times", "mwb_set_state", "mwb_num_boxes", "mwb_room_words", "mwb_step_i64", "mwb_render_top_view", "mwb_visible_ents",
     "mwb_set_mesh", "mwb_set_mesh_dims", "mwb_render_view", "mwb_debug_counters", "mwb_frame_reuse_stats",
     "mwb_grey_enable", "mwb_grey_output", "mwb_grey_convert",
+    "mwb_copy_envs", "mwb_copy_rejected", "mwb_copy_env_bytes",
 ]
 
 _lib = None
@@ -126,6 +128,10 @@ def load():
     L.mwb_grey_enable.argtypes = [vp]
     L.mwb_grey_output.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
     L.mwb_grey_convert.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
+    L.mwb_copy_envs.argtypes = [vp, vp, vp, vp, i32, ctypes.c_uint, vp]
+    L.mwb_copy_rejected.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
+    L.mwb_copy_env_bytes.argtypes = [vp, vp]
+    L.mwb_copy_env_bytes.restype = ctypes.c_longlong
     L.mwb_timing_read.argtypes = [vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(i32)]
     if L.mwb_abi_version() != ABI_VERSION:
         raise MwbError("libmwbatch.so ABI version mismatch")

@@ -88,6 +88,35 @@ ENV_SPECS = {
 _BVH_CACHE = {}
 
 
+def check_copy_indices(dst_idx, src_idx, n_dst, n_src, same_handle):
+    """The rules mwb_copy_envs applies to its (destination, source) pairs on the device (csrc/mwb_copy_check.h), for index lists
+    that live on the host: raises ValueError where the device would reject a pair - an index outside [0, n_dst) / [0, n_src), a
+    destination named by more than one pair, or, on one handle, a destination that is also some pair's source (dst == src is
+    valid there and copies nothing).  Returns the two lists as int32 arrays."""
+    d = np.asarray(dst_idx)
+    s = np.asarray(src_idx)
+    if d.ndim != 1 or s.ndim != 1 or d.shape != s.shape:
+        raise ValueError("copy_envs: dst_idx and src_idx must be one-dimensional and of equal length (%s, %s)" % (d.shape, s.shape))
+    if d.size and not (np.issubdtype(d.dtype, np.integer) and np.issubdtype(s.dtype, np.integer)):
+        raise ValueError("copy_envs: indices must be integers")
+    d, s = d.astype(np.int64), s.astype(np.int64)
+    bad = (d < 0) | (d >= n_dst)
+    if bad.any():
+        raise ValueError("copy_envs: destination index %d outside [0, %d)" % (d[bad][0], n_dst))
+    bad = (s < 0) | (s >= n_src)
+    if bad.any():
+        raise ValueError("copy_envs: source index %d outside [0, %d)" % (s[bad][0], n_src))
+    uniq, counts = np.unique(d, return_counts=True)
+    if (counts > 1).any():
+        raise ValueError("copy_envs: env %d is the destination of more than one pair" % uniq[counts > 1][0])
+    if same_handle:
+        moved = d != s   # an identity pair copies nothing
+        both = np.intersect1d(d[moved], s[moved])
+        if both.size:
+            raise ValueError("copy_envs: env %d is a destination and a source of the same call" % both[0])
+    return d.astype(np.int32), s.astype(np.int32)
+
+
 class _DevView:
     """Exposes a library-owned device buffer through __cuda_array_interface__ (zero-copy)."""
 
@@ -108,8 +137,13 @@ class BatchedMiniWorld:
 
     def __init__(self, env_id="MiniWorld-OneRoom-v0", num_envs=1, seed=None, domain_rand=False, obs_width=80,
                  obs_height=60, want_depth=False, layout="HWC", device=0, max_episode_steps=None, params=None,
-                 task=None, task_args=None, first_env_index=0, auto_reset=True, greyscale=False):
+                 task=None, task_args=None, first_env_index=0, auto_reset=True, greyscale=False, _assets=True):
         import torch
+        # what archive() builds a sibling from (before the env id's defaults are folded in: the sibling folds them in again)
+        self._ctor = dict(env_id=env_id, domain_rand=domain_rand, obs_width=obs_width, obs_height=obs_height, want_depth=want_depth,
+                          layout=layout, device=device, max_episode_steps=max_episode_steps, params=params, task=task,
+                          task_args=task_args, auto_reset=auto_reset, greyscale=greyscale)
+        self._stack_args = None
         self.torch = torch
         self.L = _lib.load()
         if task is None:
@@ -162,9 +196,10 @@ class BatchedMiniWorld:
         self.greyscale = bool(greyscale)
         if self.greyscale:   # before anything renders: the render kernels fill the grey buffer in the pass that writes obs
             _lib.check(self.L.mwb_grey_enable(self.h))
-        self._load_textures()
-        if task in TASK_MESHES:
-            self._load_meshes(task)
+        if _assets:   # (an archive is never rendered or reset: it needs neither textures nor meshes)
+            self._load_textures()
+            if task in TASK_MESHES:
+                self._load_meshes(task)
         out = _lib.MwbOutputs()
         _lib.check(self.L.mwb_get_outputs(self.h, ctypes.byref(out)))
         N, W, H = self.num_envs, self.W, self.H
@@ -355,6 +390,57 @@ class BatchedMiniWorld:
                                            {"HWC": _lib.LAYOUT_HWC, "CWH": _lib.LAYOUT_CWH}[layout], self._stream()))
         return out
 
+    # ----------------------------------------------------------------- clone, snapshot, restore
+    def _copy_index(self, idx):
+        t = self.torch.as_tensor(idx)
+        return t.to(device=self.device, dtype=self.torch.int32).reshape(-1).contiguous()
+
+    def copy_envs(self, dst_idx, src_idx, src=None, render=True):
+        """Env dst_idx[i] of this batch becomes a twin of env src_idx[i] of `src` (another BatchedMiniWorld of the same
+        configuration, e.g. an archive(); None = this batch) without leaving the device (mwb_copy_envs): from then on the two
+        agree bit for bit when stepped with the same actions.  Index lists that are tensors on this device are used in place
+        (int32, contiguous; other dtypes are converted on the device) and validated on the device: a pair that breaks a rule is
+        skipped and counted (copy_rejected()).  Host sequences / ndarrays are checked first by check_copy_indices, which raises
+        ValueError before anything is launched.  render=True: the destinations' obs / depth / grey are rendered as render()
+        renders them, nobody else's outputs change; render=False: only state moves, their frames are stale until rendered.
+        Frame stack: see mwb_copy_envs (the window of a destination env becomes a copy of the source env's when both batches
+        have the same stack; the source's must be current: stack_update() after its last pass).  Returns obs."""
+        torch = self.torch
+        src = self if src is None else src
+        on_dev = [torch.is_tensor(i) and i.device == self.device for i in (dst_idx, src_idx)]
+        if not all(on_dev):   # a list that lives on the host is checked on the host (a device list: by the validation kernel)
+            to_host = lambda i: i.cpu().numpy() if torch.is_tensor(i) else i   # noqa: E731
+            check_copy_indices(to_host(dst_idx), to_host(src_idx), self.num_envs, src.num_envs, src is self)
+        d, s = self._copy_index(dst_idx), self._copy_index(src_idx)
+        if d.numel() != s.numel():
+            raise ValueError("copy_envs: dst_idx and src_idx differ in length")
+        _lib.check(self.L.mwb_copy_envs(self.h, ctypes.c_void_p(d.data_ptr()), src.h, ctypes.c_void_p(s.data_ptr()), int(d.numel()),
+                                        0 if render else _lib.COPY_NO_RENDER, self._stream()))
+        self._keep_copy = (d, s, src)   # alive until the asynchronous kernels have consumed them
+        return self.obs
+
+    def copy_rejected(self):
+        """pairs of copy_envs calls INTO this batch that the device-side validation rejected since the last call (synchronous)"""
+        out = ctypes.c_ulonglong()
+        _lib.check(self.L.mwb_copy_rejected(self.h, ctypes.byref(out)))
+        return int(out.value)
+
+    def archive(self, capacity):
+        """A sibling batch of `capacity` slots with this batch's constructor arguments (and its frame stack, if one is enabled):
+        unseeded, never reset or rendered, without textures or meshes - a place to save() env states to and restore() them from."""
+        a = BatchedMiniWorld(num_envs=int(capacity), seed=None, _assets=False, **self._ctor)
+        if self._stack_args is not None:
+            a.stack_enable(**self._stack_args)
+        return a
+
+    def save(self, archive, slots, envs):
+        """envs of this batch -> slots of the archive (state only)"""
+        archive.copy_envs(slots, envs, src=self, render=False)
+
+    def restore(self, archive, slots, envs):
+        """slots of the archive -> envs of this batch, rendered; returns obs"""
+        return self.copy_envs(envs, slots, src=archive, render=True)
+
     # ---------------------------------------------------------------------------- introspection
     def check(self):
         """Synchronous: raises if world generation ever flagged a failure (see mwb_check)."""
@@ -493,6 +579,7 @@ class BatchedMiniWorld:
         _lib.check(self.L.mwb_get_outputs(self.h, ctypes.byref(out)))
         first, planes = ctypes.c_int32(), ctypes.c_int32()
         _lib.check(self.L.mwb_stack_window(self.h, ctypes.byref(first), ctypes.byref(planes)))
+        self._stack_args = dict(nstack=nstack, dtype=dtype, sliding=sliding, fused=fused, grey=grey)
         self._stack_c, self._stack_sliding = nstack * (1 if grey else 3), bool(sliding)
         shape = (self.num_envs, planes.value, self.W, self.H)
         self._stack_base = torch.as_tensor(_DevView(out.stack, shape, "<f4" if is_f else "|u1", self), device=self.device)

@@ -81,7 +81,21 @@ struct mwb_handle {
     MwbMeshDesc *mesh_desc_dev;
     float *view_frame;   // frame constants of mwb_render_view's size (lazily allocated)
     bool frame_reuse;    // the last-frame cache exists and step passes copy from it (off: MWB_NO_FRAME_REUSE=1, or frames rendered in tiles)
+    // ---- mwb_copy_envs (all of its scratch lives here, none in MwbDev); allocated by the first copy that needs it
+    unsigned long long serial;          // unique per mwb_create: the key of another handle's cached descriptor table
+    bool have_world;                    // mwb_reset has generated worlds (or a copy has delivered some): the handle can be a source
+    int32_t *copy_dst_pairs;            // [N] pairs of the current call that name env e as their destination; zero between calls
+    uint8_t *copy_src_mark;             // [N] env e is the source of a pair of the current call (dst == src calls); zero between calls
+    int2 *copy_pairs;                   // [copy_pairs_cap] {dst, src} per pair as validated, dst = -1: not carried out
+    size_t copy_pairs_cap;
+    unsigned long long *copy_rejected;  // [1] pairs rejected since mwb_copy_rejected last read it
+    // descriptor tables for copies INTO this handle, one per source handle (by serial; 0 = free), MWB_COPY_TABLE_DESCS entries each
+    MwbCopyDesc *copy_tables;
+    struct CopyTable { unsigned long long src; int n_small, small_chunks, n_large; } copy_table[4];
+    int copy_table_next;                // the slot the next new source takes (round robin)
 };
+#define MWB_COPY_TABLE_DESCS 64
+static unsigned long long g_next_serial = 1;
 
 extern "C" const char *mwb_last_error(void) { return g_err.c_str(); }
 extern "C" int mwb_abi_version(void) { return MWB_ABI_VERSION; }
@@ -376,6 +390,10 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
     { const char *no = getenv("MWB_NO_OVERLAP"); h->overlap_reset = !(no && atoi(no)); }
     h->side = nullptr; h->ev_fork = nullptr; h->ev_join = nullptr;
     h->view_frame = nullptr;
+    h->serial = g_next_serial++; h->have_world = false;
+    h->copy_dst_pairs = nullptr; h->copy_src_mark = nullptr; h->copy_pairs = nullptr; h->copy_pairs_cap = 0; h->copy_rejected = nullptr;
+    h->copy_tables = nullptr; h->copy_table_next = 0;
+    for (auto &t : h->copy_table) { t.src = 0; t.n_small = 0; t.small_chunks = 0; t.n_large = 0; }
     h->meshes_dirty = false; h->mesh_data_dev = nullptr; d.mesh_desc = h->mesh_desc_dev; d.mesh_data = nullptr;
     h->stack = nullptr; h->stack_n = 0; h->stack_dtype = 0; h->stack_bytes = 0; h->stack_planes = 0; h->stack_pos = 0; h->stack_fused = 0;
     h->stack_cpf = 3; d.stk_cpf = 3; h->grey_bytes = 0;
@@ -422,6 +440,7 @@ extern "C" int mwb_destroy(mwb_handle *h) {
     for (void *p : h->allocs) hipFree(p);
     if (h->texels_dev) hipFree(h->texels_dev);
     if (h->mesh_data_dev) hipFree(h->mesh_data_dev);
+    if (h->copy_pairs) hipFree(h->copy_pairs);
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
@@ -673,6 +692,7 @@ extern "C" int mwb_reset(mwb_handle *h, const uint8_t *mask_dev, void *stream) {
     TMARK(1); TMARK(5);
     mwb_launch_reset(h->dev, MWB_RESET_MAX_BLOCKS, s);   // possibly every env: many blocks
     rc = check_launch("reset_kernel"); if (rc) return rc;
+    h->have_world = true;
     TMARK(6); TMARK(2);
     rc = render_tail(h, 0, s); if (rc) return rc;
     mwb_launch_clear_list(h->dev, s);
@@ -919,6 +939,147 @@ extern "C" int mwb_stack_window(mwb_handle *h, int *first_plane, int *planes_per
     if (first_plane) *first_plane = h->stack_planes ? h->stack_pos : 0;
     if (planes_per_env) *planes_per_env = h->stack_planes ? h->stack_planes : h->stack_n * h->stack_cpf;
     return MWB_OK;
+}
+
+
+// ------------------------------------------------------------------------------ copying environments
+// the first field of the two configurations that differs (num_envs and domain_rand may), or null.  Compared as the handles use
+// them: defaults filled in (max_episode_steps <= 0, task_args 0, use_default_params)
+static const char *config_difference(const mwb_handle *a, const mwb_handle *b) {
+    const MwbDev &x = a->dev, &y = b->dev;
+    if (a->cfg.abi_version != b->cfg.abi_version) return "abi_version";
+    if (x.task != y.task) return "task";
+    if (x.W != y.W) return "obs_width";
+    if (x.H != y.H) return "obs_height";
+    if (x.want_depth != y.want_depth) return "want_depth";
+    if (x.layout != y.layout) return "layout";
+    if (x.max_episode_steps != y.max_episode_steps) return "max_episode_steps";
+    if (a->cfg.device != b->cfg.device) return "device";
+    for (int i = 0; i < 4; i++) if (x.task_args[i] != y.task_args[i]) return "task_args";
+    if (x.auto_reset != y.auto_reset) return "no_auto_reset";
+    for (int i = 0; i < MWB_NPARAM; i++)
+        for (int k = 0; k < 3; k++)
+            if (x.params[i].def[k] != y.params[i].def[k] || x.params[i].lo[k] != y.params[i].lo[k] || x.params[i].hi[k] != y.params[i].hi[k]) return "params";
+    return nullptr;
+}
+
+// the descriptor table for copies from src into dst: built once per pair of handles and kept by dst (four sources; a fifth one
+// takes the oldest table's place).  Returns the slot, or a negative code.  The caller holds the device guard.
+static int copy_table_for(mwb_handle *dst, mwb_handle *src) {
+    for (int k = 0; k < 4; k++)
+        if (dst->copy_table[k].src == src->serial) return k;
+    std::vector<MwbCopyDesc> small, large;
+    uint32_t chunks = 0;
+    mwb_for_each_env_array(src->dev, dst->dev, [&](const char *s, char *d, uint32_t rows, uint32_t elem, uint64_t ss, uint64_t ds) {
+        MwbCopyDesc t;
+        t.src = s; t.dst = d; t.rows = rows; t.elem = elem; t.src_stride = ss; t.dst_stride = ds; t.first_chunk = 0; t.pad = 0;
+        if (elem <= MWB_COPY_SMALL_ELEM) { t.first_chunk = chunks; chunks += (rows + MWB_COPY_ROW_CHUNK - 1) / MWB_COPY_ROW_CHUNK; small.push_back(t); }
+        else large.push_back(t);
+    });
+    std::vector<MwbCopyDesc> all(small);
+    all.insert(all.end(), large.begin(), large.end());
+    if (all.size() > MWB_COPY_TABLE_DESCS) return set_err(MWB_EINVAL, "mwb_copy_envs: descriptor table overflow");
+    if (!dst->copy_tables) { int rc = dev_alloc(dst, &dst->copy_tables, (size_t)4 * MWB_COPY_TABLE_DESCS); if (rc) return rc; }
+    const int k = dst->copy_table_next;
+    dst->copy_table_next = (k + 1) % 4;
+    if (dst->copy_table[k].src) HIP_TRY(hipDeviceSynchronize());   // a copy in flight may still be reading the table this one replaces
+    dst->copy_table[k].src = 0;
+    HIP_TRY(hipMemcpy(dst->copy_tables + (size_t)k * MWB_COPY_TABLE_DESCS, all.data(), all.size() * sizeof(MwbCopyDesc), hipMemcpyHostToDevice));
+    dst->copy_table[k].src = src->serial; dst->copy_table[k].n_small = (int)small.size(); dst->copy_table[k].small_chunks = (int)chunks;
+    dst->copy_table[k].n_large = (int)large.size();
+    return k;
+}
+
+extern "C" int mwb_copy_envs(mwb_handle *dst, const int32_t *dst_idx_dev, mwb_handle *src, const int32_t *src_idx_dev, int count,
+                             unsigned flags, void *stream) {
+    if (!dst || !src) return set_err(MWB_EINVAL, "mwb_copy_envs: null handle");
+    if (count < 0) return set_err(MWB_EINVAL, "mwb_copy_envs: count < 0");
+    if (count > 0 && (!dst_idx_dev || !src_idx_dev)) return set_err(MWB_EINVAL, "mwb_copy_envs: null index list");
+    if (flags & ~(unsigned)MWB_COPY_NO_RENDER) return set_err(MWB_EINVAL, "mwb_copy_envs: unknown flag");
+    if (const char *f = config_difference(dst, src))
+        return set_err(MWB_EINVAL, std::string("mwb_copy_envs: the handles' configurations differ in `") + f + "`");
+    const bool render = !(flags & MWB_COPY_NO_RENDER), same = dst == src;
+    // the frame stack (rules in include/miniworld_batch.h): nothing / the window is copied / the list render starts a new history
+    bool copy_window = false;
+    if (dst->stack) {
+        const bool alike = src->stack && src->stack_n == dst->stack_n && src->stack_dtype == dst->stack_dtype && src->stack_cpf == dst->stack_cpf;
+        if (alike) copy_window = true;
+        else if (!dst->stack_fused) return set_err(MWB_EINVAL, "mwb_copy_envs: the destination's frame stack (not MWB_STACK_FUSED) can only be filled from a source with a stack of equal nstack, dtype and grey flag");
+        else if (!render) return set_err(MWB_EINVAL, "mwb_copy_envs: MWB_COPY_NO_RENDER into a fused frame stack needs a source with a stack of equal nstack, dtype and grey flag");
+    }
+    if (count == 0) return MWB_OK;
+    if (!src->have_world) return set_err(MWB_ESTATE, "mwb_copy_envs: the source has never been reset (it holds no worlds)");
+    USE_DEVICE(dst->cfg.device);
+    int rc;
+    if (render) { rc = ensure_ready(dst); if (rc) return rc; }   // MWB_ESTATE without seed / textures / meshes: what mwb_render needs
+    hipStream_t s = (hipStream_t)stream;
+    MwbDev &d = dst->dev;
+    if (!dst->copy_dst_pairs) { rc = dev_alloc(dst, &dst->copy_dst_pairs, (size_t)d.N); if (rc) return rc; }
+    if (!dst->copy_src_mark) { rc = dev_alloc(dst, &dst->copy_src_mark, (size_t)d.N); if (rc) return rc; }
+    if (!dst->copy_rejected) {
+        rc = dev_alloc(dst, &dst->copy_rejected, (size_t)1); if (rc) return rc;
+        HIP_TRY(hipDeviceSynchronize());   // the scratch is zero before a kernel on the caller's stream counts in it
+    }
+    if (dst->copy_pairs_cap < (size_t)count) {   // (hipFree waits for the kernels still reading the old one)
+        if (dst->copy_pairs) { HIP_TRY(hipFree(dst->copy_pairs)); dst->copy_pairs = nullptr; dst->copy_pairs_cap = 0; }
+        const size_t cap = (size_t)count < (size_t)d.N ? (size_t)d.N : (size_t)count;
+        HIP_TRY(hipMalloc((void **)&dst->copy_pairs, cap * sizeof(int2)));
+        dst->copy_pairs_cap = cap;
+    }
+    const int slot = copy_table_for(dst, src);
+    if (slot < 0) return slot;
+    const mwb_handle::CopyTable &tab = dst->copy_table[slot];
+    mwb_launch_copy_validate(dst_idx_dev, src_idx_dev, count, d.N, src->dev.N, same ? 1 : 0, dst->copy_dst_pairs, dst->copy_src_mark,
+                             dst->copy_pairs, dst->copy_rejected, s);
+    rc = check_launch("copy_validate_kernel"); if (rc) return rc;
+    mwb_launch_copy_envs(dst->copy_tables + (size_t)slot * MWB_COPY_TABLE_DESCS, tab.n_small, tab.small_chunks, tab.n_large, dst->copy_pairs, count, s);
+    rc = check_launch("copy_envs_kernel"); if (rc) return rc;
+    dst->have_world = true;
+    if (render) {   // the destinations through the compact-list path, as mwb_render draws them: the current state, every frame rendered
+        d.step_pass = 0; d.reuse_pass = 0;
+        dst->timing_now = false;
+        mwb_launch_copy_list(d, dst->copy_pairs, count, 0, s);
+        rc = check_launch("copy_list_kernel"); if (rc) return rc;
+        mwb_launch_prep(d, 1, s);
+        rc = check_launch("prep_kernel"); if (rc) return rc;
+        mwb_launch_render(d, 1, s);
+        rc = check_launch("render_kernel"); if (rc) return rc;
+        mwb_launch_copy_list(d, dst->copy_pairs, count, 1, s);
+        rc = check_launch("copy_list_kernel"); if (rc) return rc;
+    } else {
+        mwb_launch_copy_list(d, dst->copy_pairs, count, 2, s);
+        rc = check_launch("copy_list_kernel"); if (rc) return rc;
+    }
+    if (copy_window) {   // after the render: the history the list path has just zeroed is the source's again
+        const size_t plane = (size_t)d.W * d.H * (dst->stack_dtype == 1 ? 4 : 1), C = (size_t)dst->stack_n * dst->stack_cpf;
+        const size_t kd = dst->stack_planes ? (size_t)dst->stack_planes : C, ks = src->stack_planes ? (size_t)src->stack_planes : C;
+        const size_t pd = dst->stack_planes ? (size_t)dst->stack_pos : 0, ps = src->stack_planes ? (size_t)src->stack_pos : 0;
+        mwb_launch_copy_stack((char *)dst->stack, kd * plane, pd * plane, (const char *)src->stack, ks * plane, ps * plane, C * plane, dst->copy_pairs, count, s);
+        rc = check_launch("copy_stack_kernel"); if (rc) return rc;
+    }
+    return MWB_OK;
+}
+
+extern "C" int mwb_copy_rejected(mwb_handle *dst, unsigned long long *pairs) {
+    if (!dst || !pairs) return set_err(MWB_EINVAL, "mwb_copy_rejected: null argument");
+    *pairs = 0;
+    if (!dst->copy_rejected) return MWB_OK;   // no copy yet
+    USE_DEVICE(dst->cfg.device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(pairs, dst->copy_rejected, sizeof(*pairs), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(dst->copy_rejected, 0, sizeof(*pairs)));
+    HIP_TRY(hipDeviceSynchronize());
+    return MWB_OK;
+}
+
+// bytes of per-env state one accepted pair of a copy from src into dst moves (the descriptor table's total); for measurements
+extern "C" long long mwb_copy_env_bytes(mwb_handle *dst, mwb_handle *src) {
+    if (!dst || !src) return set_err(MWB_EINVAL, "mwb_copy_env_bytes: null argument");
+    if (const char *f = config_difference(dst, src))
+        return set_err(MWB_EINVAL, std::string("mwb_copy_env_bytes: the handles' configurations differ in `") + f + "`");
+    size_t total = 0;
+    mwb_for_each_env_array(src->dev, dst->dev, [&](const char *, char *, uint32_t rows, uint32_t elem, uint64_t, uint64_t) { total += (size_t)rows * elem; });
+    return (long long)total;
 }
 
 // -------------------------------------------------------------------------------- introspection

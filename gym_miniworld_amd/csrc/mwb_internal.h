@@ -227,6 +227,67 @@ struct MwbDev {
     int exp_flags;   // MWB_EXP env var at mwb_create: bit 0 = meshes are never hit, bit 1 = flat grey mesh shading (timing experiments)
 };
 
+// ---- mwb_copy_envs: every per-env array of MwbDev that a later kernel READS as state, in one place.  An array added to the
+// struct above that carries state from one pass to the next must be added here too, or a copied env is no twin of its source.
+// Not listed on purpose: `frame` (prep rebuilds it before every render), cost / bucket / order_bufs (a dispatch heuristic), the
+// outputs of the last transition (reward, reward64, done, ep_steps, feature, goal_pos: the next step rewrites them), reset_set /
+// reset_list / frame_cached / frame_same and the frame caches (the copy pass and the render it runs maintain them), seg_stage
+// (scratch of one reset_kernel launch).
+// One descriptor per array: env e of the array is `rows` pieces of `elem` bytes, piece r at base + r * row_stride + e * elem.
+// An env-major block (rng [N][625], rooms [N][R_max][words], cam [N][4] ...) is one row of many bytes; an env-minor array
+// (agent_x [N], box_x [B][N], box_color [B][N][3], segs [S_max][4][N]) is many rows N * elem apart - N differs between two
+// handles, so both strides travel.
+struct MwbCopyDesc {
+    const char *src;
+    char *dst;
+    uint32_t rows, elem;
+    uint64_t src_stride, dst_stride;
+    uint32_t first_chunk;   // small rows (elem <= MWB_COPY_SMALL_ELEM): index of the array's first row chunk in copy_envs_kernel's grid
+    uint32_t pad;
+};
+#define MWB_COPY_SMALL_ELEM 32   // pieces up to this size are copied one per lane (lane = pair); larger ones by a workgroup per pair
+#define MWB_COPY_ROW_CHUNK 8     // rows of one small array a workgroup of copy_envs_kernel takes
+
+// f(src base, dst base, rows, elem bytes, src row stride, dst row stride) for every array; s and d of equal configuration but N
+template <class F>
+static inline void mwb_for_each_env_array(const MwbDev &s, const MwbDev &d, F &&f) {
+#define MWB_MINOR(p, rows, per) f((const char *)s.p, (char *)d.p, (uint32_t)(rows), (uint32_t)(sizeof(*s.p) * (per)), \
+                                  (uint64_t)sizeof(*s.p) * (per) * (uint64_t)s.N, (uint64_t)sizeof(*s.p) * (per) * (uint64_t)d.N)
+#define MWB_MAJOR(p, count) f((const char *)s.p, (char *)d.p, 1u, (uint32_t)(sizeof(*s.p) * (count)), (uint64_t)0, (uint64_t)0)
+    const int B = s.n_boxes;
+    MWB_MINOR(agent_x, 1, 1); MWB_MINOR(agent_z, 1, 1); MWB_MINOR(agent_dir, 1, 1);
+    MWB_MINOR(box_x, B, 1); MWB_MINOR(box_z, B, 1); MWB_MINOR(box_dir, B, 1); MWB_MINOR(box_y, B, 1);
+    MWB_MINOR(box_color, B, 3); MWB_MINOR(box_size, B, 1);
+    MWB_MINOR(carrying, 1, 1); MWB_MINOR(goal_dist, 1, 1);
+    MWB_MINOR(episode_count, 1, 1); MWB_MINOR(task_step_count, 1, 1); MWB_MINOR(goal_idx, 1, 1);
+    MWB_MAJOR(cam, 4); MWB_MAJOR(sky_color, 3); MWB_MAJOR(light_pos, 3); MWB_MAJOR(light_color, 3); MWB_MAJOR(light_ambient, 3);
+    MWB_MINOR(step_count, 1, 1); MWB_MINOR(n_rooms, 1, 1); MWB_MINOR(n_segs, 1, 1); MWB_MINOR(n_rrooms, 1, 1);
+    MWB_MAJOR(world_ext, 4);
+    MWB_MAJOR(rng, MWB_MT_WORDS);
+    MWB_MAJOR(rooms, (size_t)s.R_max * s.room_words);
+    MWB_MINOR(segs, s.S_max * 4, 1);
+    if (s.ent_task) {
+        MWB_MINOR(ent_meta, B, 1); MWB_MINOR(ent_radius, B, 1); MWB_MINOR(ent_height, B, 1); MWB_MINOR(ent_scale, B, 1);
+        MWB_MAJOR(ent_order, MWB_ORDER_STRIDE); MWB_MINOR(n_order, 1, 1);
+        MWB_MINOR(task_f, 1, 1); MWB_MINOR(task_i, 1, 1); MWB_MAJOR(text_tex, 8);
+        MWB_MINOR(ovr_slot, 1, 1); MWB_MAJOR(ovr_pose, 4);
+    }
+#undef MWB_MINOR
+#undef MWB_MAJOR
+}
+
+// launch wrappers implemented in mwb_copy.hip (mwb_copy_envs).  `pairs`: per pair of the call {dst, src} as copy_validate_kernel
+// left them - dst = -1 for a pair that is not carried out (rejected, or an identity pair)
+void mwb_launch_copy_validate(const int32_t *dst_idx, const int32_t *src_idx, int count, int n_dst, int n_src, int same_handle,
+                              int32_t *dst_pairs, uint8_t *src_mark, int2 *pairs, unsigned long long *rejected, hipStream_t s);
+void mwb_launch_copy_envs(const MwbCopyDesc *table, int n_small, int small_chunks, int n_large, const int2 *pairs, int count, hipStream_t s);
+// what: 0 = put the destinations on d's reset_set / reset_list (before the list render), 1 = take them off again and empty the
+// list (after it), 2 = no render: their cached frames no longer show their state
+void mwb_launch_copy_list(const MwbDev &d, const int2 *pairs, int count, int what, hipStream_t s);
+// the visible window of the frame stack: env_bytes_* = bytes between consecutive envs, off_* = byte offset of the window's first plane
+void mwb_launch_copy_stack(char *dst, size_t env_bytes_dst, size_t off_dst, const char *src, size_t env_bytes_src, size_t off_src,
+                           size_t window_bytes, const int2 *pairs, int count, hipStream_t s);
+
 // launch wrappers implemented in mwb_kernels.hip
 void mwb_launch_step(const MwbDev &d, const int32_t *actions, const uint8_t *skip_mask, hipStream_t s);   // entity tasks: step_ents_kernel
 void mwb_launch_clear_list(const MwbDev &d, hipStream_t s);

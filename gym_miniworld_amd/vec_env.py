@@ -285,6 +285,19 @@ class MiniWorldVecEnv(VecEnv):
             infos = self._infos_plain
         return obs, rews, dones, infos
 
+    def copy_envs(self, dst_idx, src_idx, src=None):
+        """Env dst_idx[i] becomes a twin of env src_idx[i] of `src` - another MiniWorldVecEnv, an archive (self.batch.archive(n)) or
+        None for this one - on the device (BatchedMiniWorld.copy_envs, rendered).  Returns the current observation in this view's
+        own form; the frame-stack window does not move (stack_update is not called): a destination env shows its source's
+        stacked frames."""
+        b = self.batch
+        b.copy_envs(dst_idx, src_idx, src=getattr(src, "batch", src), render=True)
+        if self.nstack:
+            return b.stack
+        if self.greyscale:
+            return b.grey
+        return b.obs.float() if self.to_float else b.obs
+
     def close(self):
         self._graph = None
         self.batch.close()

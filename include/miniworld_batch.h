@@ -318,6 +318,48 @@ int mwb_grey_output(mwb_handle *h, float **grey, size_t *bytes);
 int mwb_grey_convert(mwb_handle *h, const uint8_t *rgb_dev, float *grey_dev, int n_frames, int width, int height, int layout,
                      void *stream);
 
+/* ---- copying environments on the device: clone, snapshot, restore ------------------------------ */
+/* replaces: copy.deepcopy(env), or assigning a saved env's attributes (agent, entities, rooms, rand) to another env, on the
+ * reference's Python objects.
+ * For each i < count, env dst_idx[i] of `dst` becomes a TWIN of env src_idx[i] of `src`: stepped with the same actions the two
+ * agree bit for bit at every later step - reward, done, ep_steps, the whole mwb_get_state (MT19937 words and entity order
+ * included), mwb_get_geometry, obs, depth and grey - through episode ends and auto-resets.  Everything a later kernel reads of an env
+ * is copied, the world (room table, collision segments) included; the outputs of the destination's last transition (reward,
+ * done, ep_steps, feature, goal_pos) are not: the next step rewrites them.  Both index arrays are int32 in DEVICE memory, so
+ * a selection computed on the device needs no synchronisation; all work is enqueued on `stream`.  dst == src clones inside one
+ * handle; a second handle of the same configuration serves as an archive (there is no other object type).
+ *
+ * The two handles' mwb_config must be equal except for num_envs and domain_rand, on one device: MWB_EINVAL otherwise, the
+ * message names the first differing field.  That both were given the same textures and meshes is the caller's duty.
+ * MWB_ESTATE: the source has never been reset (nor received a copy); or a rendering copy into a destination that lacks
+ * what mwb_render needs (seed, textures, meshes).  count == 0 is a no-op, count < 0 or a null argument MWB_EINVAL.  A slot of an
+ * archive that never received a copy holds no world: copying FROM it is the caller's error (it yields an empty env).
+ *
+ * Pairs are validated on the device before anything is copied (csrc/mwb_copy_check.h).  A pair is REJECTED - skipped entirely and
+ * counted - when an index is outside [0, num_envs) of its handle, when its destination is named by more than one pair, or when,
+ * on one handle, its destination is also some pair's source; except that dst_idx[i] == src_idx[i] on one handle is valid and does
+ * nothing.  mwb_copy_rejected returns the number of pairs rejected on `dst` since it was last called and clears it (synchronous).
+ *
+ * Observations.  Without MWB_COPY_NO_RENDER the accepted destinations are prepared and rendered on `stream` as mwb_render
+ * renders them (the current state): when the call's work completes, obs, depth, grey and the last-frame cache of every destination
+ * env hold what mwb_render would write for it, and every other env's outputs are untouched.  With MWB_COPY_NO_RENDER only state
+ * moves: the destination's frames are stale until the caller renders (their cached last frames are dropped), and the
+ * destination needs nothing beyond mwb_create - an archive never uploads a texture.
+ *
+ * Frame stack.  The window does not move in a copy.  (1) No stack on the destination: nothing is done.  (2) Both handles have a
+ * stack of equal nstack, dtype and grey flag (the form - shifting, sliding, fused - may differ): the destination env's visible
+ * window, planes [first_plane, first_plane + nstack * 3 or nstack), becomes a byte copy of the source env's, after the render.
+ * PRECONDITION: the source's stack is current - for the non-fused forms mwb_stack_update has been called after the source's last
+ * pass.  (3) The destination's stack is fused and the source has none or another one: the destination env gets what a
+ * regenerated env gets, a zeroed history and its frame in the newest planes; MWB_EINVAL under MWB_COPY_NO_RENDER.  (4) The
+ * destination's stack is not fused and the source has none or another one: MWB_EINVAL. */
+#define MWB_COPY_NO_RENDER 1
+int mwb_copy_envs(mwb_handle *dst, const int32_t *dst_idx_dev, mwb_handle *src, const int32_t *src_idx_dev,
+                  int count, unsigned flags, void *stream);
+int mwb_copy_rejected(mwb_handle *dst, unsigned long long *pairs);   /* synchronous; reads and clears */
+/* bytes of per-env state one accepted pair of a copy from src into dst moves (for measurements); negative code on mismatch */
+long long mwb_copy_env_bytes(mwb_handle *dst, mwb_handle *src);
+
 /* World generation cannot fail for the four tasks with sane arguments; if it ever does (a portal outside
  * its wall, more than one portal on an edge, a placement that finds no free spot in 100000 draws - the
  * reference would assert or spin) the kernel flags it. Synchronous: returns MWB_ESTATE if any env of the
