@@ -7,21 +7,15 @@ sizes and MB_*_OFF offsets, so a size cannot drift, but a region added, dropped 
 test.  The sizes the regions need are stated here once more, on purpose: from what the kernels store in them."""
 import ctypes
 import math
-import os
-import subprocess
 
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+from lds_host import build_lds_host, frame_words
+
 RENDER_FIELDS = ["rooms", "fc", "tex", "sync", "queues", "ikeys", "ipix", "item_res", "fb", "mqueues", "mleft", "mdesc", "mb", "total"]
 RESET_FIELDS = ["rooms", "cdf", "seg_off", "key", "dfs", "e_x", "e_y", "e_z", "e_dir", "e_size", "e_rad", "e_hgt", "e_scale",
                 "e_bias", "e_meta", "e_f32", "e_col", "e_text", "total"]
 CONSTANTS = ["waves", "queue_cap", "mq_cap", "mb_half", "mb_tasks", "mb_wave_bytes", "mb_slots", "mb_pairs", "mb_pix", "mb_count", "tex_bytes", "wroom_bytes", "max_ents", "num_meshes", "strip_w"]
-
-
-def frame_words(n_boxes):   # MWB_FRAME_WORDS_FOR
-    return (36 + 34 * n_boxes + 3) & ~3
 
 
 # name: R_max, room words, frame words, textures, entity task, W, H (the frame, or the tile a launch is sized for), pinned total
@@ -41,15 +35,7 @@ RESET = {"maze8x8": (127, 0, 1, 39424), "fourrooms": (8, 0, 0, 4768), "pickupobj
 
 @pytest.fixture(scope="module")
 def host():
-    out = os.path.join(HERE, "_build")
-    os.makedirs(out, exist_ok=True)
-    so = os.path.join(out, "liblds_layout_host.so")
-    srcs = [os.path.join(HERE, "lds_layout_host.cpp"), os.path.join(ROOT, "gym_miniworld_amd", "csrc", "mwb_lds_layout.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Werror", "-o", so, srcs[0]])
-    L = ctypes.CDLL(so)
-    L.lds_launch_bytes.restype = ctypes.c_long
-    return L
+    return build_lds_host()   # tests/lds_host.py: shared with test_gpu_frame_sizes.py
 
 
 @pytest.fixture(scope="module")
