@@ -366,6 +366,9 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
     if (rc == MWB_OK) rc = dev_alloc(h, &d.order_bufs[0], N);
     if (rc == MWB_OK) rc = dev_alloc(h, &d.order_bufs[1], N);
     if (rc == MWB_OK) rc = dev_alloc(h, &d.order_state, (size_t)2);
+    if (rc == MWB_OK) rc = dev_alloc(h, &d.render_list, N);
+    if (rc == MWB_OK) rc = dev_alloc(h, &d.reuse_list, N);
+    if (rc == MWB_OK) rc = dev_alloc(h, &d.list_counts, (size_t)2);
     if (rc == MWB_OK) {   // no cost known yet: identity order
         std::vector<int32_t> ident(N);
         for (size_t i = 0; i < N; i++) ident[i] = (int32_t)i;

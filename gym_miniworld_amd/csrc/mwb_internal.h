@@ -225,6 +225,11 @@ struct MwbDev {
     int tile_w, tile_h;   // entity tasks: every frame is rendered as tiles of this size, one workgroup each (0: whole frames)
     unsigned long long *dbg_counters;   // [8] or null: walk_meshes counters (MWB_EXP bit 2)
     int exp_flags;   // MWB_EXP env var at mwb_create: bit 0 = meshes are never hit, bit 1 = flat grey mesh shading (timing experiments)
+    // ---- work lists of a step's bulk render launch (mwb_dispatch_map.h), rebuilt by prep_kernel(mode 2) ahead of every such launch from
+    // the order map in use, reset_set and frame_same: dispatch scratch like order_bufs, nothing carries over from step to step
+    int32_t *render_list;   // [N] the envs the launch renders, dearest first; the first list_counts[0] entries are valid
+    int32_t *reuse_list;    // [N] the envs whose last frame it copies; list_counts[1] entries
+    int32_t *list_counts;   // [2]
 };
 
 // ---- mwb_copy_envs: every per-env array of MwbDev that a later kernel READS as state, in one place.  An array added to the

@@ -18,6 +18,7 @@
 #include "mwb_internal.h"
 #include "mwb_glibc_trig.h"
 #include "mwb_lds_layout.h"
+#include "mwb_dispatch_map.h"
 
 // float64 sin / cos as the reference's process computes them (math.sin / math.cos -> glibc 2.35 __sin_fma / __cos_fma,
 // restated bit for bit in mwb_glibc_trig.h); OCML's differ in the last bit for a few arguments in a thousand, which an
@@ -1945,7 +1946,62 @@ void mwb_launch_order(const MwbDev &d, hipStream_t s) {
     hipLaunchKernelGGL(order_kernel, dim3(1), dim3(1024), 0, s, d);
 }
 
+// The bulk render's work lists (mwb_dispatch_map.h), by the one extra block of prep_kernel(mode 2): a stable compaction of the
+// order map in use into the envs the launch renders (d.render_list, dearest first as in the map) and those whose last frame it
+// copies (d.reuse_list), with the two lengths in d.list_counts.  Regenerated envs go to neither.  Tiles of 256 x LIST_ROWS
+// entries: every lane has its LIST_ROWS order entries and their flags in flight at once (row r of a tile is entries
+// r * 256 + tid: coalesced), a row's ranks come from wave ballots, and the 4 x LIST_ROWS x 2 wave counts are scanned in LDS.
+#define LIST_ROWS 16   // 8192 envs are two tiles
+__device__ __forceinline__ void build_render_lists(const MwbDev &d) {
+    constexpr int NW = 256 / WAVE, CELLS = LIST_ROWS * NW;   // (row, wave) cells of a tile, in list order
+    __shared__ int cnt[2][CELLS], base[2];
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+    const int32_t *__restrict__ order = d.order_bufs[d.order_state[0] & 1];
+    const bool reuse = d.reuse_pass && d.frame_same;
+    if (tid < 2) base[tid] = 0;
+    for (int t0 = 0; t0 < d.N; t0 += 256 * LIST_ROWS) {
+        int env[LIST_ROWS];
+        uint8_t regen[LIST_ROWS], same[LIST_ROWS];
+#pragma unroll
+        for (int r = 0; r < LIST_ROWS; r++) { const int i = t0 + r * 256 + tid; env[r] = i < d.N ? order[i] : -1; }
+#pragma unroll
+        for (int r = 0; r < LIST_ROWS; r++) {
+            regen[r] = env[r] >= 0 ? d.reset_set[env[r]] : (uint8_t)1;
+            same[r] = (reuse && env[r] >= 0) ? d.frame_same[env[r]] : (uint8_t)0;
+        }
+        unsigned long long mr[LIST_ROWS], mc[LIST_ROWS];
+#pragma unroll
+        for (int r = 0; r < LIST_ROWS; r++) {
+            mr[r] = __ballot(!regen[r] && !same[r]);
+            mc[r] = __ballot(!regen[r] && same[r]);   // (the step kernels never set frame_same for an env they regenerate)
+            if (lane == 0) { cnt[0][r * NW + wave] = __popcll(mr[r]); cnt[1][r * NW + wave] = __popcll(mc[r]); }
+        }
+        __syncthreads();
+        // exclusive prefix of each list's CELLS counts, by one wave per list (CELLS <= WAVE)
+        static_assert(CELLS <= WAVE, "one lane per cell");
+        if (wave < 2) {
+            const int own = lane < CELLS ? cnt[wave][lane] : 0;
+            int inc = own;
+#pragma unroll
+            for (int ofs = 1; ofs < WAVE; ofs <<= 1) { const int v = __shfl_up(inc, ofs); if (lane >= ofs) inc += v; }
+            const int b0 = base[wave];
+            if (lane < CELLS) cnt[wave][lane] = b0 + inc - own;
+            if (lane == WAVE - 1) base[wave] = b0 + inc;   // read above by this wave only
+        }
+        __syncthreads();
+        const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+        for (int r = 0; r < LIST_ROWS; r++) {
+            if ((mr[r] >> lane) & 1ull) d.render_list[cnt[0][r * NW + wave] + __popcll(mr[r] & below)] = env[r];
+            if ((mc[r] >> lane) & 1ull) d.reuse_list[cnt[1][r * NW + wave] + __popcll(mc[r] & below)] = env[r];
+        }
+        __syncthreads();   // cnt is rewritten by the next tile
+    }
+    if (tid < 2) d.list_counts[tid] = base[tid];
+}
+
 __global__ void __launch_bounds__(256) prep_kernel(MwbDev d, int mode) {
+    if (mode == 2 && blockIdx.x == (unsigned)((d.N + 255) / 256)) { build_render_lists(d); return; }   // the one block behind the envs' (mwb_launch_prep)
     int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (mode == 1) {
         __builtin_amdgcn_s_setprio(3);   // beside the bulk render (see reset_kernel)   // the regenerated envs, through the compact list
@@ -3803,18 +3859,34 @@ __device__ __forceinline__ void render_body(const MwbDev &d, unsigned char *smem
         // little from step to step): a frame's time varies from 0.5x to 2.5x the mean, and starting the slow ones
         // first keeps the launch from ending on a few stragglers.  The last d.split_envs of that order - the
         // cheapest frames - run as two half-frame workgroups each.
-        const int whole = d.N - d.split_envs;
         const int b = blockIdx.x;
-        const int slot = b < whole ? b : whole + ((b - whole) >> 1);
-        const int part = b < whole ? -1 : ((b - whole) & 1);
-        const int e = __builtin_amdgcn_readfirstlane(d.order_bufs[d.order_state[0] & 1][slot]);
-        if (MODE == 2 && d.reset_set[e]) return;   // block-uniform
-        if (d.reuse_pass && d.frame_same && d.frame_same[e]) {   // block-uniform; decided by this step's step kernel (never for a regenerated env)
-            if (part <= 0) {   // of a half-frame pair the first copies the frame, the second has nothing to do
-                reuse_frame<THREADS, GREY>(d, e);
+        int e, part;
+        if constexpr (MODE == 2) {
+            // A step's bulk launch takes its work from the two lists prep_kernel(mode 2) has just built from that order (only the
+            // envs that render keep a place in it; mwb_dispatch_map.h): whole frames, then the halves of the last d.split_envs
+            // of them, and behind every rendering workgroup the copies of the reused frames.  Block-uniform throughout.
+            const int R = __builtin_amdgcn_readfirstlane(d.list_counts[0]), C = __builtin_amdgcn_readfirstlane(d.list_counts[1]);
+            const MwbDispatch m = mwb_dispatch_map(b, R, C, d.split_envs, (int)gridDim.x);
+            if (m.role == MWB_ROLE_EXIT) return;
+            e = __builtin_amdgcn_readfirstlane((m.role == MWB_ROLE_COPY ? d.reuse_list : d.render_list)[m.index]);
+            part = m.part;
+            if (m.role == MWB_ROLE_COPY) {   // one env per copy block, not a loop over several: a loop around reuse_frame costs the
+                reuse_frame<THREADS, GREY>(d, e);   // maze kernel 139 SGPR spills, this form 107 (parent 87; 96 VGPRs either way, parent 94)
                 if (threadIdx.x == 0) atomicAdd(d.reuse_stats, 1ull);
+                return;   // d.cost[e] keeps the last measured cost: order_kernel does not file the env under "cheapest"
             }
-            return;   // d.cost[e] keeps the last measured cost: order_kernel does not file the env under "cheapest"
+        } else {
+            const int whole = d.N - d.split_envs;
+            const int slot = b < whole ? b : whole + ((b - whole) >> 1);
+            part = b < whole ? -1 : ((b - whole) & 1);
+            e = __builtin_amdgcn_readfirstlane(d.order_bufs[d.order_state[0] & 1][slot]);
+            if (d.reuse_pass && d.frame_same && d.frame_same[e]) {   // block-uniform; decided by this step's step kernel (never for a regenerated env)
+                if (part <= 0) {   // of a half-frame pair the first copies the frame, the second has nothing to do
+                    reuse_frame<THREADS, GREY>(d, e);
+                    if (threadIdx.x == 0) atomicAdd(d.reuse_stats, 1ull);
+                }
+                return;   // d.cost[e] keeps the last measured cost
+            }
         }
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();   // read by every wave: stays in scalar registers
         render_env<THREADS, NBOX, false, POLY, false, GREY>(d, e, part, smem);
@@ -4107,7 +4179,8 @@ void mwb_launch_reset(const MwbDev &d, int max_blocks, hipStream_t s) {
     hipLaunchKernelGGL(reset_fn(d.task), dim3(d.N < max_blocks ? d.N : max_blocks), dim3(WAVE), mwb_reset_lds_bytes(d), s, d);
 }
 void mwb_launch_prep(const MwbDev &d, int mode, hipStream_t s) {
-    const int blocks = mode == 1 ? 8 : (d.N + 255) / 256;
+    // mode 2 with whole-frame workgroups: one more block, which builds the work lists of the bulk render launch behind it
+    const int blocks = mode == 1 ? 8 : (d.N + 255) / 256 + (mode == 2 && d.tile_w == 0 ? 1 : 0);
     hipLaunchKernelGGL(prep_kernel, dim3(blocks), dim3(256), 0, s, d, mode);
 }
 void mwb_launch_render(const MwbDev &d, int mode, hipStream_t s) {
