@@ -29,6 +29,7 @@ MESH_GEOMS = ["ball", "key", "medkit", "duckie", "building", "cone"]   # MWB_MES
 TEX_MESH0, TEX_CHAR0 = 21, 25
 LAYOUT_HWC, LAYOUT_CWH = 0, 1
 COPY_NO_RENDER = 1   # MWB_COPY_NO_RENDER
+MAX_REPEAT = 64      # MWB_MAX_REPEAT
 
 
 class MwbConfig(ctypes.Structure):
@@ -69,6 +70,7 @@ EXPORTS = [
     "mwb_set_mesh", "mwb_set_mesh_dims", "mwb_render_view", "mwb_debug_counters", "mwb_frame_reuse_stats",
     "mwb_grey_enable", "mwb_grey_output", "mwb_grey_convert",
     "mwb_copy_envs", "mwb_copy_rejected", "mwb_copy_env_bytes",
+    "mwb_step_repeat", "mwb_repeat_taken",
 ]
 
 _lib = None
@@ -101,6 +103,8 @@ def load():
     L.mwb_reset.argtypes = [vp, vp, vp]
     L.mwb_step.argtypes = [vp, vp, vp, vp]
     L.mwb_step_i64.argtypes = [vp, vp, vp, vp]
+    L.mwb_step_repeat.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+    L.mwb_repeat_taken.argtypes = [vp, ctypes.POINTER(vp)]
     L.mwb_render.argtypes = [vp, vp]
     L.mwb_render_top_view.argtypes = [vp, vp, i32, i32, vp]
     L.mwb_visible_ents.argtypes = [vp, vp, vp]

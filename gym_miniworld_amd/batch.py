@@ -117,6 +117,20 @@ def check_copy_indices(dst_idx, src_idx, n_dst, n_src, same_handle):
     return d.astype(np.int32), s.astype(np.int32)
 
 
+def check_repeat_args(repeat, num_envs, n_actions, n_skip=None, n_counts=None, name="step_repeat: repeat"):
+    """What step_repeat refuses before anything is launched: raises ValueError for a `repeat` that is no integer in
+    1 .. MAX_REPEAT (mwb_step_repeat would answer MWB_EINVAL) and for actions / skip_mask / counts that do not have one entry
+    per env.  `name`: what the messages call `repeat` (the VecEnv views check their frame_skip with it).  Returns repeat as an int."""
+    if isinstance(repeat, bool) or not isinstance(repeat, (int, np.integer)):
+        raise ValueError("%s must be an integer, not %r" % (name, repeat))
+    if not 1 <= int(repeat) <= _lib.MAX_REPEAT:
+        raise ValueError("%s %d outside 1 .. %d" % (name, repeat, _lib.MAX_REPEAT))
+    for what, n in (("actions", n_actions), ("skip_mask", n_skip), ("counts", n_counts)):
+        if n is not None and int(n) != int(num_envs):
+            raise ValueError("step_repeat: %s has %d entries for %d envs" % (what, n, num_envs))
+    return int(repeat)
+
+
 class _DevView:
     """Exposes a library-owned device buffer through __cuda_array_interface__ (zero-copy)."""
 
@@ -223,6 +237,9 @@ class BatchedMiniWorld:
         # the six small outputs above are parts of one allocation: a host-side consumer copies `pack` once per step
         self.pack = as_t(out.pack, (out.pack_bytes,), "|u1")
         self.pack_offsets = {k: int(getattr(out, k)) - int(out.pack) for k in ("reward64", "goal_pos", "reward", "feature", "ep_steps", "done")}
+        tp = ctypes.c_void_p()
+        _lib.check(self.L.mwb_repeat_taken(self.h, ctypes.byref(tp)))
+        self.taken = as_t(tp.value, (N,), "<i4")   # sub-steps every env took in the last step_repeat (zero-copy)
         self.n_boxes = int(self.L.mwb_num_boxes(self.h))   # 1; 2 (TMazeTwoBox, SimToRealPush); 6 (PutNext)
         self.agent_radius = 0.11 if task.startswith("SimToReal") else 1.5 if task == "RoomObjs" else 0.4
         self.ent_task = _lib.TASK_IDS[task] >= _lib.ENT_TASK_FIRST
@@ -333,6 +350,28 @@ class BatchedMiniWorld:
         _lib.check((self.L.mwb_step_i64 if i64 else self.L.mwb_step)(self.h, ctypes.c_void_p(a.data_ptr()), m, self._stream()))
         self._keep = (a, skip_mask)   # keep inputs alive until the async kernels have consumed them
         return self.obs, self.reward, self.done
+
+    def step_repeat(self, actions, repeat, skip_mask=None, counts=None):
+        """Action repeat on the device (mwb_step_repeat): every env takes up to `repeat` sub-steps of step() with its one action -
+        counts[i] of them, clamped to 1 .. repeat on the device, when `counts` (int [N]) is given - stops at the sub-step that
+        ends its episode, and only the frame after its last sub-step is rendered.  reward / reward64 are the sums over the
+        sub-steps, done / ep_steps / feature / goal_pos the last sub-step's, `taken` the number of sub-steps.  int32 and int64
+        actions on this device are read in place.  Returns the views (obs, reward, done, taken)."""
+        torch = self.torch
+        a = torch.as_tensor(actions)
+        m = None if skip_mask is None else torch.as_tensor(skip_mask)
+        c = None if counts is None else torch.as_tensor(counts)
+        repeat = check_repeat_args(repeat, self.num_envs, a.numel(), None if m is None else m.numel(), None if c is None else c.numel())
+        i64 = a.dtype == torch.int64 and a.device == self.device
+        a = (a if i64 else a.to(device=self.device, dtype=torch.int32)).reshape(-1).contiguous()
+        if m is not None:
+            m = m.to(device=self.device, dtype=torch.uint8).reshape(-1).contiguous()
+        if c is not None:
+            c = c.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())   # noqa: E731
+        _lib.check(self.L.mwb_step_repeat(self.h, None if i64 else ptr(a), ptr(a) if i64 else None, ptr(m), repeat, ptr(c), self._stream()))
+        self._keep = (a, m, c)   # keep inputs alive until the async kernels have consumed them
+        return self.obs, self.reward, self.done, self.taken
 
     def step_longtensor(self, actions):
         """step() for the one shape a trainer's loop produces every time - a contiguous int64 tensor [N] on this device - without

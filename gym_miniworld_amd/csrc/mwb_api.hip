@@ -93,6 +93,10 @@ struct mwb_handle {
     MwbCopyDesc *copy_tables;
     struct CopyTable { unsigned long long src; int n_small, small_chunks, n_large; } copy_table[4];
     int copy_table_next;                // the slot the next new source takes (round robin)
+    // ---- mwb_step_repeat: the per-env scratch of repeat_fold_kernel (mwb_repeat_fold.h); not part of an env's state, never copied
+    double *rep_sum;                    // [N] float64 sum of the call's sub-step rewards
+    int32_t *rep_taken;                 // [N] sub-steps taken in the last call (mwb_repeat_taken)
+    uint8_t *rep_same, *rep_frozen;     // [N] each: every sub-step so far left the frame standing / the env takes no further sub-step
 };
 #define MWB_COPY_TABLE_DESCS 64
 static unsigned long long g_next_serial = 1;
@@ -358,6 +362,7 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
     A(h->tex_desc_dev, (size_t)MWB_MAX_TEX);
     A(h->scratch_int_dev, (size_t)4);
     A(d.error_flag, (size_t)1);
+    A(h->rep_sum, N); A(h->rep_taken, N); A(h->rep_same, N); A(h->rep_frozen, N);
 #undef A
     if (rc == MWB_OK && (d.debug_flags & 16)) rc = dev_alloc(h, &d.wg_ts, 2 * (N + (size_t)d.split_envs));
     if (rc == MWB_OK && (d.exp_flags & 4)) rc = dev_alloc(h, &d.dbg_counters, (size_t)8);
@@ -705,7 +710,8 @@ extern "C" int mwb_reset(mwb_handle *h, const uint8_t *mask_dev, void *stream) {
     return check_launch("order_kernel");
 }
 
-static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *skip_mask_dev, void *stream);
+// repeat == 0: one step (mwb_step); 1 .. MWB_MAX_REPEAT: the sub-steps of mwb_step_repeat
+static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *skip_mask_dev, void *stream, int repeat = 0, const int32_t *counts_dev = nullptr);
 extern "C" int mwb_step(mwb_handle *h, const int32_t *actions_dev, const uint8_t *skip_mask_dev, void *stream) {
     if (!h) return set_err(MWB_EINVAL, "null handle");
     h->dev.act_stride = 1;
@@ -716,7 +722,20 @@ extern "C" int mwb_step_i64(mwb_handle *h, const int64_t *actions_dev, const uin
     h->dev.act_stride = 2;   // little-endian: the low word of each int64 (actions are small non-negative integers)
     return step_impl(h, (const int32_t *)actions_dev, skip_mask_dev, stream);
 }
-static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *skip_mask_dev, void *stream) {
+extern "C" int mwb_step_repeat(mwb_handle *h, const int32_t *actions_dev, const int64_t *actions_i64_dev, const uint8_t *skip_mask_dev, int repeat,
+                               const int32_t *counts_dev, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "null handle");
+    if (repeat < 1 || repeat > MWB_MAX_REPEAT) return set_err(MWB_EINVAL, "mwb_step_repeat: repeat must lie in 1 .. " + std::to_string(MWB_MAX_REPEAT));
+    if ((actions_dev != nullptr) == (actions_i64_dev != nullptr)) return set_err(MWB_EINVAL, "mwb_step_repeat: exactly one of actions / actions_i64 must be given");
+    h->dev.act_stride = actions_i64_dev ? 2 : 1;
+    return step_impl(h, actions_i64_dev ? (const int32_t *)actions_i64_dev : actions_dev, skip_mask_dev, stream, repeat, counts_dev);
+}
+extern "C" int mwb_repeat_taken(mwb_handle *h, int32_t **dev) {
+    if (!h || !dev) return set_err(MWB_EINVAL, "mwb_repeat_taken: null argument");
+    *dev = h->rep_taken;
+    return MWB_OK;
+}
+static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *skip_mask_dev, void *stream, int repeat, const int32_t *counts_dev) {
     USE_DEVICE(h->cfg.device);
     int rc = ensure_ready(h); if (rc) return rc;
     if (!actions_dev) return set_err(MWB_EINVAL, "mwb_step: null actions");
@@ -727,6 +746,19 @@ static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *s
     rc = stack_advance(h, 0, s); if (rc) return rc;
     mwb_launch_step(h->dev, actions_dev, skip_mask_dev, s);
     rc = check_launch("step_kernel"); if (rc) return rc;
+    // mwb_step_repeat: fold every sub-step's outputs (mwb_repeat_fold.h), then step the envs that are not frozen yet again.  A
+    // masked env is frozen by the first fold, so the later launches need no skip mask; the order flip, the stack window and the
+    // reset list move once (the flip is a no-op once order_state[1] is down, a finished env is frozen before it could be listed twice).
+    for (int sub = 0; sub < repeat; sub++) {
+        if (sub) {
+            MwbDev dv = h->dev;
+            dv.frozen = h->rep_frozen;
+            mwb_launch_step(dv, actions_dev, nullptr, s);
+            rc = check_launch("step_kernel"); if (rc) return rc;
+        }
+        mwb_launch_repeat_fold(h->dev, sub, sub == repeat - 1, repeat, skip_mask_dev, counts_dev, h->rep_sum, h->rep_taken, h->rep_same, h->rep_frozen, s);
+        rc = check_launch("repeat_fold_kernel"); if (rc) return rc;
+    }
     TMARK(1);
     if (!h->overlap_reset) {
         TMARK(5);

@@ -230,6 +230,9 @@ struct MwbDev {
     int32_t *render_list;   // [N] the envs the launch renders, dearest first; the first list_counts[0] entries are valid
     int32_t *reuse_list;    // [N] the envs whose last frame it copies; list_counts[1] entries
     int32_t *list_counts;   // [2]
+    // ---- mwb_step_repeat (last on purpose: no other member's offset moves).  Null except in the launches of sub-steps 2..k of
+    // such a call, where the step kernels leave env e untouched when frozen[e] is set (mwb_repeat_fold.h, repeat_fold_kernel)
+    const uint8_t *frozen;  // [N]
 };
 
 // ---- mwb_copy_envs: every per-env array of MwbDev that a later kernel READS as state, in one place.  An array added to the
@@ -292,6 +295,10 @@ void mwb_launch_copy_list(const MwbDev &d, const int2 *pairs, int count, int wha
 // the visible window of the frame stack: env_bytes_* = bytes between consecutive envs, off_* = byte offset of the window's first plane
 void mwb_launch_copy_stack(char *dst, size_t env_bytes_dst, size_t off_dst, const char *src, size_t env_bytes_src, size_t off_src,
                            size_t window_bytes, const int2 *pairs, int count, hipStream_t s);
+
+// launch wrapper implemented in mwb_repeat.hip (mwb_step_repeat): folds sub-step `sub` of a call into the handle's scratch
+void mwb_launch_repeat_fold(const MwbDev &d, int sub, int last, int repeat, const uint8_t *skip, const int32_t *counts, double *sum,
+                            int32_t *taken, uint8_t *same, uint8_t *frozen, hipStream_t s);
 
 // launch wrappers implemented in mwb_kernels.hip
 void mwb_launch_step(const MwbDev &d, const int32_t *actions, const uint8_t *skip_mask, hipStream_t s);   // entity tasks: step_ents_kernel

@@ -150,8 +150,11 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
     const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
     const int e = blockIdx.x * 64 + lane;
     const bool in_range = e < d.N;
-    const bool dummy = in_range && skip && skip[e];   // the fork's 'dummy' command, vec_env/subproc_vec_env.py:26-31
-    const bool live = in_range && !dummy;
+    // mwb_step_repeat, sub-steps after the first: an env whose sub-steps are over is left exactly as it is - state, RNG, outputs,
+    // reset_set, frame_same (its lanes still reach the barriers below).  d.frozen is null in every other launch.
+    const bool frozen = in_range && d.frozen && d.frozen[e];
+    const bool dummy = in_range && !frozen && skip && skip[e];   // the fork's 'dummy' command, vec_env/subproc_vec_env.py:26-31
+    const bool live = in_range && !dummy && !frozen;
     int sc = 0, a = -1;
     double ax = 0, az = 0, adir = 0, nx = 0, nz = 0, turn_step = 0;
     constexpr int NB = NBX;   // entity order: the boxes (red; red, blue / yellow; PutNext's six), then the agent
@@ -434,6 +437,7 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x == 0 && d.order_state[1]) { d.order_state[0] ^= 1; d.order_state[1] = 0; }
     if (e >= d.N) return;
+    if (d.frozen && d.frozen[e]) return;   // mwb_step_repeat: this env's sub-steps are over, nothing of it is touched (null elsewhere)
     const size_t N = (size_t)d.N;
     const int E = d.n_boxes;
     if (skip && skip[e]) {   // the fork's 'dummy' command, vec_env/subproc_vec_env.py:26-31

@@ -54,8 +54,11 @@ class MiniWorldEnv:
         done = 7
 
     def __init__(self, env_id="MiniWorld-OneRoom-v0", domain_rand=False, obs_width=80, obs_height=60, device=0,
-                 seed=None, **kwargs):
-        from .batch import BatchedMiniWorld
+                 seed=None, frame_skip=1, **kwargs):
+        from .batch import BatchedMiniWorld, check_repeat_args
+        # frame_skip=k: step() repeats the action up to k times, stops at done, sums the rewards and returns the last frame and
+        # info (plus info['taken']) - the frame-skip wrapper's loop, run on the device without the frames in between
+        self.frame_skip = check_repeat_args(frame_skip, 1, 1, name="frame_skip")
         self._b = BatchedMiniWorld(env_id, num_envs=1, domain_rand=domain_rand, obs_width=obs_width,
                                    obs_height=obs_height, want_depth=True, layout="HWC", device=device,
                                    auto_reset=False, **kwargs)
@@ -191,7 +194,10 @@ class MiniWorldEnv:
 
     def step(self, action):
         import torch
-        self._b.step(torch.tensor([int(action)], dtype=torch.int32))
+        if self.frame_skip > 1:
+            self._b.step_repeat(torch.tensor([int(action)], dtype=torch.int32), self.frame_skip)
+        else:
+            self._b.step(torch.tensor([int(action)], dtype=torch.int32))
         obs = self._b.obs.cpu().numpy()[0]
         reward, done = float(self._b.reward64.cpu()[0]), bool(self._b.done.cpu()[0])
         self._sync()
@@ -202,6 +208,8 @@ class MiniWorldEnv:
             info["feature"] = self._b.feature.cpu().numpy()[0].astype(np.float64)
         if self._b.has_health:   # collecthealth.py:75
             info["health"] = float(self._b.feature.cpu().numpy()[0, 0])
+        if self.frame_skip > 1:
+            info["taken"] = int(self._b.taken.cpu()[0])
         if self._b.task == "Sign":
             obs = {"obs": obs, "goal": int(self._b.task_args[2])}
         return obs, reward, done, info

@@ -74,10 +74,12 @@ class LazyInfos:
     all costs milliseconds per step, several times the device step.  The batched arrays behind the dicts are
     exposed too, so that a trainer can replace its per-env loop
         for info in infos: _feature.append(info["feature"])          (pytorch-a2c-ppo-acktr/main.py:612-617)
-    by `infos.feature`:  goal_pos [N,3] float64 or None, feature [N,2] float64 or None, skipped bool [N] or None."""
+    by `infos.feature`:  goal_pos [N,3] float64 or None, feature [N,2] float64 or None, skipped bool [N] or None, and with
+    frame_skip taken int32 [N] (info['taken']: the sub-steps behind the transition, for gamma ** taken) or None."""
 
-    def __init__(self, n, goal_pos=None, feature=None, skipped=None, default_feature=False, health=None):
+    def __init__(self, n, goal_pos=None, feature=None, skipped=None, default_feature=False, health=None, taken=None):
         self.n, self.goal_pos, self.skipped = n, goal_pos, skipped
+        self.taken = taken
         self.health = health   # CollectHealth: info['health'] (collecthealth.py:75), float64 [N] or None
         self._task_feature = feature is not None
         self.feature = feature if feature is not None else (np.zeros((n, 2)) if default_feature else None)
@@ -99,6 +101,8 @@ class LazyInfos:
             info["goal_pos"] = self.goal_pos[i].copy()
         if self.health is not None:
             info["health"] = float(self.health[i])
+        if self.taken is not None:
+            info["taken"] = int(self.taken[i])
         if self._task_feature:
             info["feature"] = self.feature[i].copy()
         elif self.feature is not None:
@@ -122,6 +126,9 @@ class MiniWorldVecEnv(VecEnv):
                        step overwrites it, so a caller that keeps observations by reference must clone them
     torch_api=True  -> actions arrive as LongTensor [N,1], rewards leave as CPU FloatTensor [N,1]
                        (VecPyTorch); False -> numpy in / numpy out like SubprocVecEnv
+    frame_skip=k    -> action repeat: a step() is up to k sub-steps of the env with the one action, stopped by done, of which only
+                       the last frame is rendered (mwb_step_repeat); the reward is the sum, info['taken'] the number of
+                       sub-steps (infos.taken for the whole batch).  The frame stack holds one frame per step().
     feature_info    -> every info dict carries "feature" (length-2 zeros) as the fork's PPO loop
                        requires (pytorch-a2c-ppo-acktr/main.py:614-619)
     graph=True      -> after two eager steps the whole step (mwb_step's kernels on both streams, the frame-stack /
@@ -135,12 +142,15 @@ class MiniWorldVecEnv(VecEnv):
     """
 
     def __init__(self, env_id, num_envs, seed=1, device=0, domain_rand=False, transpose=True, to_float=True,
-                 frame_stack=0, torch_api=True, feature_info=False, first_env_index=0, graph=False, greyscale=False, **kwargs):
+                 frame_stack=0, torch_api=True, feature_info=False, first_env_index=0, graph=False, greyscale=False, frame_skip=1,
+                 **kwargs):
         import torch
         from .batch import BatchedMiniWorld
         from . import _lib
         self.torch = torch
         self.greyscale = bool(greyscale)
+        from .batch import check_repeat_args
+        self.frame_skip = check_repeat_args(frame_skip, num_envs, num_envs, name="frame_skip")
         assert to_float or not self.greyscale, "greyscale observations are float32 (GreyscaleWrapper + .float()): to_float=True"
         self.batch = BatchedMiniWorld(env_id, num_envs=num_envs, seed=seed, domain_rand=domain_rand, device=device,
                                       layout="CWH" if transpose else "HWC", first_env_index=first_env_index, greyscale=self.greyscale, **kwargs)
@@ -186,6 +196,7 @@ class MiniWorldVecEnv(VecEnv):
         self._h_goal = part("goal_pos", np.float64, 3 * n).reshape(n, 3) if b.has_goal_pos else None
         self._h_feat = part("feature", np.float32, 2 * n).reshape(n, 2) if (b.has_features or b.has_health) else None
         self._h_skip = pin((num_envs,), torch.uint8)
+        self._h_taken = pin((num_envs,), torch.int32) if self.frame_skip > 1 else None   # filled by a copy of its own, beside the pack's
         self._ev = torch.cuda.Event()
         self._skip_host = None
         self._use_graph, self._graph, self._eager_steps = bool(graph), None, 0
@@ -210,12 +221,16 @@ class MiniWorldVecEnv(VecEnv):
         """everything of a step that runs on the device: the stepper + renderer, the learner-side layout pass and the
         asynchronous copies of the small outputs into the pinned host mirrors"""
         b = self.batch
-        if skip is None and a.dtype == self.torch.int64:
+        if self.frame_skip > 1:
+            b.step_repeat(a, self.frame_skip, skip_mask=skip)
+        elif skip is None and a.dtype == self.torch.int64:
             b.step_longtensor(a)
         else:
             b.step(a, skip_mask=skip)
         obs = self._obs_out(done=b.done)
         self._h_pack.copy_(b.pack[:self._pack_need], non_blocking=True)   # one copy: the small outputs share an allocation
+        if self._h_taken is not None:
+            self._h_taken.copy_(b.taken, non_blocking=True)   # same stream, ahead of step_wait's one wait
         return obs
 
     def step_async(self, actions, mask=None):
@@ -273,14 +288,15 @@ class MiniWorldVecEnv(VecEnv):
         else:
             rews = self._h_rew.copy()
         sk = self._skip_host
+        tk = self._h_taken.numpy().copy() if self._h_taken is not None else None   # info['taken']
         if b.has_health:   # CollectHealth: info['health'] (delivered in feature[:, 0])
-            infos = LazyInfos(self.num_envs, health=self._h_feat[:, 0].astype(np.float64), skipped=sk, default_feature=self.feature_info)
+            infos = LazyInfos(self.num_envs, health=self._h_feat[:, 0].astype(np.float64), skipped=sk, default_feature=self.feature_info, taken=tk)
         elif b.has_goal_pos:   # the T-maze family: info['goal_pos'] (tmaze.py:66,206) and, where produced, info['feature']
             infos = LazyInfos(self.num_envs, goal_pos=self._h_goal.copy(),
                               feature=self._h_feat.astype(np.float64) if self._h_feat is not None else None,
-                              skipped=sk, default_feature=self.feature_info)
-        elif sk is not None and sk.any():
-            infos = LazyInfos(self.num_envs, skipped=sk, default_feature=self.feature_info)
+                              skipped=sk, default_feature=self.feature_info, taken=tk)
+        elif tk is not None or (sk is not None and sk.any()):
+            infos = LazyInfos(self.num_envs, skipped=sk, default_feature=self.feature_info, taken=tk)
         else:
             infos = self._infos_plain
         return obs, rews, dones, infos

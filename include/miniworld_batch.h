@@ -249,6 +249,31 @@ int mwb_step(mwb_handle *h, const int32_t *actions_dev, const uint8_t *skip_mask
 /* the same with the LongTensor the reference's policy produces (VecPyTorch.step_async, envs.py:121-125): int64 actions [N] in
  * device memory are read in place (no conversion pass); a value outside int32 is an unknown action (never aliased) */
 int mwb_step_i64(mwb_handle *h, const int64_t *actions_dev, const uint8_t *skip_mask_dev, void *stream);
+/* Action repeat ("frame skip").  replaces: the loop a trainer wraps around env.step inside the worker of
+ * vec_env/subproc_vec_env.py:5-33, under the worker's auto-reset:
+ *     total = 0.0
+ *     for _ in range(n_i): obs, r, done, info = env.step(a); total += r
+ *                          if done: break
+ * In one call env i takes at most n_i sub-steps of MiniWorldEnv.step with its one action and only the frame after the last of
+ * them is rendered.  n_i = repeat, or counts[i] clamped to [1, repeat] on the device when counts (device i32[num_envs]) is not
+ * NULL.  An env stops at the sub-step that sets done (task rule or time limit, as mwb_step decides them).  Outputs: reward64 =
+ * the float64 sum of the sub-steps' rewards in order, starting from 0.0; reward = that sum as float; done, ep_steps, feature and
+ * goal_pos = those of the last sub-step taken; obs / depth / grey / the fused frame stack's newest planes = the last sub-step's
+ * own frame (entity tasks: with that sub-step's render override and no earlier one), or, for a finished env under auto-reset,
+ * the first frame of the new episode - it is regenerated once, after its last sub-step.  With no_auto_reset the env just stops.
+ * An env named by skip_mask takes the skip path once (reward -99, done 0, no sub-step).  The frame stack and the dispatch order
+ * move once per call.  An env's last frame is reused only if every sub-step of the call left it unchanged.
+ * Exactly one of actions (i32) and actions_i64 (read in place as mwb_step_i64 reads them) is not NULL.  repeat lies in
+ * 1 .. MWB_MAX_REPEAT (it bounds the kernel launches of a call: two per sub-step): MWB_EINVAL otherwise, and nothing changes.
+ * repeat == 1 with counts == NULL leaves every output, the state and the frame-reuse counters exactly as mwb_step does.
+ * Capturable into a HIP graph as mwb_step is (repeat is a host constant of the capture). */
+#define MWB_MAX_REPEAT 64
+int mwb_step_repeat(mwb_handle *h, const int32_t *actions_dev, const int64_t *actions_i64_dev, const uint8_t *skip_mask_dev, int repeat,
+                    const int32_t *counts_dev, void *stream);
+/* replaces: the `taken` a frame-skip wrapper would count in the loop above (a learner discounts by gamma ** taken).
+ * *dev: library-owned device i32[num_envs], the sub-steps every env took in the last mwb_step_repeat (0 for an env its skip
+ * mask named; zeros before the first call); the pointer is fixed for the handle's lifetime. */
+int mwb_repeat_taken(mwb_handle *h, int32_t **dev);
 /* replaces: MiniWorldEnv.render_obs / render_depth (miniworld.py:1160-1220) for the whole batch */
 int mwb_render(mwb_handle *h, void *stream);
 /* Last-frame reuse.  A step that leaves an env exactly as it was - a move that a wall or an entity blocks, nothing carried; an env
