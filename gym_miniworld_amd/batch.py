@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib
 from .params import DEFAULT_PARAMS, sim_to_real_params
+from .tasks import task_facts
 
 TEX_FILES = ["floor_tiles_bw_1", "concrete_1", "concrete_2", "concrete_3", "concrete_4", "concrete_tiles_1",
              "brick_wall_1",
@@ -23,10 +24,6 @@ TEX_FILES = ["floor_tiles_bw_1", "concrete_1", "concrete_2", "concrete_3", "conc
              "../meshes/medkit", "../meshes/duckie", "../meshes/building", "../meshes/cone"] + \
             ["chars/ch_0x%d_%d" % (ord(c), v) for c in "BLUERDGN" for v in range(1, 10)]
 TEX_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "textures")
-# (mesh geometry, height) pairs each entity task builds: Ball(size) / Key 0.35 / BigKey 0.6 (entity.py:410-434, sign.py:9-20), MeshEnt(...)
-TASK_MESHES = {"PickupObjs": [("ball", 0.9), ("key", 0.35)], "RoomObjs": [("ball", 0.9), ("key", 0.35)], "CollectHealth": [("medkit", 0.40)],
-               "ThreeRooms": [("duckie", 0.25), ("key", 0.35), ("ball", 0.6)], "Sign": [("key", 0.6)],
-               "Sidewalk": [("building", 30), ("cone", 0.75)], "WallGap": [("building", 30)]}
 
 
 def _sign_params():   # Sign.__init__, sign.py:62-64
@@ -173,6 +170,7 @@ class BatchedMiniWorld:
                 domain_rand = spec_dr
         self.env_id, self.task = env_id, task
         self.task_args = list(task_args or []) + [0, 0, 0, 0]
+        facts = task_facts(task, task_args, max_episode_steps)   # (tasks.py; the library resolves its own part in mwb_create)
         self.num_envs = int(num_envs)
         self.W, self.H = int(obs_width), int(obs_height)
         self.want_depth = bool(want_depth)
@@ -195,9 +193,8 @@ class BatchedMiniWorld:
         cfg.domain_rand = int(self.domain_rand)
         cfg.max_episode_steps = int(max_episode_steps or 0)
         cfg.device = self.device_index
-        ta = list(task_args or []) + [0, 0, 0, 0]
         for i in range(4):
-            cfg.task_args[i] = float(ta[i])
+            cfg.task_args[i] = float(self.task_args[i])
         cfg.use_default_params = 0
         cfg.no_auto_reset = 0 if auto_reset else 1
         table = self.params.to_table()
@@ -212,8 +209,8 @@ class BatchedMiniWorld:
             _lib.check(self.L.mwb_grey_enable(self.h))
         if _assets:   # (an archive is never rendered or reset: it needs neither textures nor meshes)
             self._load_textures()
-            if task in TASK_MESHES:
-                self._load_meshes(task)
+            if facts.meshes:
+                self._load_meshes(facts.meshes)
         out = _lib.MwbOutputs()
         _lib.check(self.L.mwb_get_outputs(self.h, ctypes.byref(out)))
         N, W, H = self.num_envs, self.W, self.H
@@ -241,26 +238,11 @@ class BatchedMiniWorld:
         _lib.check(self.L.mwb_repeat_taken(self.h, ctypes.byref(tp)))
         self.taken = as_t(tp.value, (N,), "<i4")   # sub-steps every env took in the last step_repeat (zero-copy)
         self.n_boxes = int(self.L.mwb_num_boxes(self.h))   # 1; 2 (TMazeTwoBox, SimToRealPush); 6 (PutNext)
-        self.agent_radius = 0.11 if task.startswith("SimToReal") else 1.5 if task == "RoomObjs" else 0.4
         self.ent_task = _lib.TASK_IDS[task] >= _lib.ENT_TASK_FIRST
-        # action_space: Discrete(move_forward + 1) in the navigation tasks (e.g. hallway.py:23), Discrete(move_back + 1)
-        # in SimToRealPush (simtorealpush.py:37), the base class' Discrete(len(Actions)) = 8 where the task does not
-        # narrow it (PutNext: miniworld.py:470)
-        self.n_actions = {"SimToRealPush": 4, "PutNext": 8, "PickupObjs": 5, "RoomObjs": 8, "CollectHealth": 8, "Sign": 4}.get(task, 3)
-        self.has_health = task == "CollectHealth"   # info['health'] arrives in feature[:, 0]
-        self.has_features = task == "TMazeTwoBox" and ta[0] != 0
-        self.has_goal_pos = task in ("TMaze", "TMazeTwoBox", "YMaze")   # tmaze.py:66,206, ymaze.py:92
-        self.max_episode_steps = self._max_steps(task, ta, max_episode_steps)
+        self.max_episode_steps, self.agent_radius, self.n_actions = facts.max_episode_steps, facts.agent_radius, facts.n_actions
+        self.has_health, self.has_features, self.has_goal_pos = facts.has_health, facts.has_features, facts.has_goal_pos
         if seed is not None:
             self.seed(seed)
-
-    @staticmethod
-    def _max_steps(task, ta, mes):
-        if mes:
-            return int(mes)
-        return {"Hallway": 250, "OneRoom": 180, "FourRooms": 250, "TMaze": 280, "TMazeTwoBox": 280,
-                "SimToRealGoTo": 100, "SimToRealPush": 150, "PutNext": 250, "YMaze": 280, "PickupObjs": 400, "RoomObjs": 2 ** 31 - 1,
-                "CollectHealth": 1000, "ThreeRooms": 400, "Sign": 20, "Sidewalk": 150, "WallGap": 300}.get(task) or int(ta[0] or 8) * int(ta[1] or 8) * 24
 
     def _load_textures(self):
         from PIL import Image
@@ -270,13 +252,13 @@ class BatchedMiniWorld:
             _lib.check(self.L.mwb_set_texture(self.h, tid, img.shape[1], img.shape[0],
                                               img.ctypes.data_as(ctypes.c_void_p)))
 
-    def _load_meshes(self, task):
+    def _load_meshes(self, meshes):
         """ObjMesh.get for every mesh the task's entities use (objmesh.py:16-216) + the BVH the render kernel walks, and
         MeshEnt.__init__'s scale / radius (entity.py:118-127) evaluated here with the reference's expressions"""
         from . import meshes as M
         vp = ctypes.c_void_p
         done = set()
-        for geom, height in TASK_MESHES[task]:
+        for geom, height in meshes:
             name = geom + "_red" if geom in ("ball", "key") else geom   # the colour variants share their geometry
             m = M.get(name)
             if geom not in done:

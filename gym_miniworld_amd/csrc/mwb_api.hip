@@ -14,7 +14,11 @@
 
 #include "mwb_internal.h"
 #include "mwb_lds_layout.h"
+#include "mwb_task_table.h"
 #include "mwb_texture_host.h"
+
+static_assert(mwb_task_frame_words(1) == MWB_FRAME_WORDS_FOR(1) && mwb_task_frame_words(MWB_MAX_ENTS) == MWB_FRAME_WORDS_FOR(MWB_MAX_ENTS),
+              "mwb_task_table.h restates the frame constants' size");
 
 static thread_local std::string g_err;
 static int set_err(int code, const std::string &msg) { g_err = msg; return code; }
@@ -42,61 +46,60 @@ struct DevGuard {
         return set_err(MWB_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(_dev_guard.err))
 
 struct mwb_handle {
-    mwb_config cfg;
-    MwbDev dev;
+    mwb_config cfg = {};
+    MwbDev dev = {};
     std::vector<void *> allocs;
     std::vector<std::vector<uint32_t>> tex_levels[MWB_MAX_TEX];   // host mip chains (RGBA8 packed)
-    int tex_w[MWB_MAX_TEX], tex_h[MWB_MAX_TEX];
-    uint32_t *texels_dev;
-    MwbTexDesc *tex_desc_dev;
-    bool seeded, textures_dirty, have_textures;
-    bool have_obs;   // some pass has rendered an observation since creation
-    int *scratch_int_dev;
-    // timing
+    int tex_w[MWB_MAX_TEX] = {}, tex_h[MWB_MAX_TEX] = {};
+    uint32_t *texels_dev = nullptr;
+    MwbTexDesc *tex_desc_dev = nullptr;
+    bool seeded = false, textures_dirty = false, have_textures = false;
+    bool have_obs = false;   // some pass has rendered an observation since creation
+    int *scratch_int_dev = nullptr;
     // timing: five events per pipeline pass, drawn from a pool and only read back in
     // mwb_timing_read, so that enabling it adds no host synchronisation to the timed region
-    bool timing, timing_now;   // enabled at all / recording the current pass
-    int timing_period, timing_tick;   // record every timing_period-th pass (the events themselves cost ~20 us per pass)
+    bool timing = false, timing_now = false;   // enabled at all / recording the current pass
+    int timing_period = 1, timing_tick = 0;   // record every timing_period-th pass (the events themselves cost ~20 us per pass)
     std::vector<hipEvent_t> ev_pool;
-    size_t ev_used;
-    hipEvent_t *ev;   // the current pass' events: 0-4 on the caller's stream, 5-6 around reset_kernel
+    size_t ev_used = 0;
+    hipEvent_t *ev = nullptr;   // the current pass' events: 0-4 on the caller's stream, 5-6 around reset_kernel
     // mwb_step overlaps world generation of the finished envs with the bulk render on a side stream
-    bool overlap_reset;
-    void *pack;          // done | reward | feature | goal_pos | ep_steps | reward64 in one allocation
-    size_t pack_bytes;
-    void *stack;
-    int stack_n, stack_dtype;
-    int stack_fused;               // the render kernels write the frames into the window themselves (MWB_STACK_FUSED)
-    int stack_planes, stack_pos;   // sliding-window stack: planes per env (0 = the classic shifting stack), the window's first plane
-    int stack_cpf;                 // channel planes per frame: 3, or 1 (MWB_STACK_GREY: fed from the grey frame)
-    size_t grey_bytes;             // the grey buffer h->dev.grey (mwb_grey_enable), 0 while it is off
-    size_t stack_bytes;
-    hipStream_t side;
-    hipEvent_t ev_fork, ev_join;
+    bool overlap_reset = true;
+    void *pack = nullptr;          // done | reward | feature | goal_pos | ep_steps | reward64 in one allocation
+    size_t pack_bytes = 0;
+    void *stack = nullptr;
+    int stack_n = 0, stack_dtype = 0;
+    int stack_fused = 0;               // the render kernels write the frames into the window themselves (MWB_STACK_FUSED)
+    int stack_planes = 0, stack_pos = 0;   // sliding-window stack: planes per env (0 = the classic shifting stack), the window's first plane
+    int stack_cpf = 3;                 // channel planes per frame: 3, or 1 (MWB_STACK_GREY: fed from the grey frame)
+    size_t grey_bytes = 0;             // the grey buffer h->dev.grey (mwb_grey_enable), 0 while it is off
+    size_t stack_bytes = 0;
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // entity tasks: mesh geometries (host copies until the first pass uploads them in one allocation)
     struct HostMesh { bool set = false; int n_tris = 0, n_nodes = 0, n_orders = 1, tex_id = -1; float min_c[3], max_c[3]; std::vector<float> nodes, tris, tris2, shade; };
     HostMesh meshes[MWB_NUM_MESHES];
-    bool meshes_dirty;
-    float4 *mesh_data_dev;
-    MwbMeshDesc *mesh_desc_dev;
-    float *view_frame;   // frame constants of mwb_render_view's size (lazily allocated)
-    bool frame_reuse;    // the last-frame cache exists and step passes copy from it (off: MWB_NO_FRAME_REUSE=1, or frames rendered in tiles)
+    bool meshes_dirty = false;
+    float4 *mesh_data_dev = nullptr;
+    MwbMeshDesc *mesh_desc_dev = nullptr;
+    float *view_frame = nullptr;   // frame constants of mwb_render_view's size (lazily allocated)
+    bool frame_reuse = false;    // the last-frame cache exists and step passes copy from it (off: MWB_NO_FRAME_REUSE=1, or frames rendered in tiles)
     // ---- mwb_copy_envs (all of its scratch lives here, none in MwbDev); allocated by the first copy that needs it
-    unsigned long long serial;          // unique per mwb_create: the key of another handle's cached descriptor table
-    bool have_world;                    // mwb_reset has generated worlds (or a copy has delivered some): the handle can be a source
-    int32_t *copy_dst_pairs;            // [N] pairs of the current call that name env e as their destination; zero between calls
-    uint8_t *copy_src_mark;             // [N] env e is the source of a pair of the current call (dst == src calls); zero between calls
-    int2 *copy_pairs;                   // [copy_pairs_cap] {dst, src} per pair as validated, dst = -1: not carried out
-    size_t copy_pairs_cap;
-    unsigned long long *copy_rejected;  // [1] pairs rejected since mwb_copy_rejected last read it
+    unsigned long long serial = 0;      // unique per mwb_create: the key of another handle's cached descriptor table
+    bool have_world = false;            // mwb_reset has generated worlds (or a copy has delivered some): the handle can be a source
+    int32_t *copy_dst_pairs = nullptr;  // [N] pairs of the current call that name env e as their destination; zero between calls
+    uint8_t *copy_src_mark = nullptr;   // [N] env e is the source of a pair of the current call (dst == src calls); zero between calls
+    int2 *copy_pairs = nullptr;         // [copy_pairs_cap] {dst, src} per pair as validated, dst = -1: not carried out
+    size_t copy_pairs_cap = 0;
+    unsigned long long *copy_rejected = nullptr;  // [1] pairs rejected since mwb_copy_rejected last read it
     // descriptor tables for copies INTO this handle, one per source handle (by serial; 0 = free), MWB_COPY_TABLE_DESCS entries each
-    MwbCopyDesc *copy_tables;
-    struct CopyTable { unsigned long long src; int n_small, small_chunks, n_large; } copy_table[4];
-    int copy_table_next;                // the slot the next new source takes (round robin)
+    MwbCopyDesc *copy_tables = nullptr;
+    struct CopyTable { unsigned long long src = 0; int n_small = 0, small_chunks = 0, n_large = 0; } copy_table[4];
+    int copy_table_next = 0;            // the slot the next new source takes (round robin)
     // ---- mwb_step_repeat: the per-env scratch of repeat_fold_kernel (mwb_repeat_fold.h); not part of an env's state, never copied
-    double *rep_sum;                    // [N] float64 sum of the call's sub-step rewards
-    int32_t *rep_taken;                 // [N] sub-steps taken in the last call (mwb_repeat_taken)
-    uint8_t *rep_same, *rep_frozen;     // [N] each: every sub-step so far left the frame standing / the env takes no further sub-step
+    double *rep_sum = nullptr;          // [N] float64 sum of the call's sub-step rewards
+    int32_t *rep_taken = nullptr;       // [N] sub-steps taken in the last call (mwb_repeat_taken)
+    uint8_t *rep_same = nullptr, *rep_frozen = nullptr;   // [N] each: every sub-step so far left the frame standing / the env takes no further sub-step
 };
 #define MWB_COPY_TABLE_DESCS 64
 static unsigned long long g_next_serial = 1;
@@ -236,115 +239,65 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
     if (cfg->device < 0 || cfg->device >= ndev) return set_err(MWB_EINVAL, "mwb_create: bad device ordinal");
     USE_DEVICE(cfg->device);
 
+    MwbTaskFacts t;
+    {
+        std::string why;
+        if (int rc = mwb_resolve_task(*cfg, &t, &why)) return set_err(rc, why);
+    }
+
     mwb_handle *h = new mwb_handle();
     h->cfg = *cfg;
+    h->serial = g_next_serial++;
     MwbDev &d = h->dev;
-    memset(&d, 0, sizeof(d));
     d.N = cfg->num_envs; d.task = cfg->task; d.W = cfg->obs_width; d.H = cfg->obs_height;
     d.want_depth = cfg->want_depth ? 1 : 0; d.layout = cfg->layout; d.domain_rand = cfg->domain_rand ? 1 : 0;
     d.auto_reset = cfg->no_auto_reset ? 0 : 1;
+    // the task (mwb_task_table.h)
+    d.ent_task = t.ent_task; d.n_boxes = t.n_boxes; d.R_max = t.R_max; d.S_max = t.S_max; d.max_episode_steps = t.max_episode_steps;
+    d.n_tex = t.n_tex; d.no_ceiling = t.no_ceiling; d.poly = t.poly; d.room_words = t.room_words; d.frame_words = t.frame_words;
+    d.agent_radius = t.agent_radius;
+    memcpy(d.task_args, t.task_args, sizeof(d.task_args));
+    double P[MWB_NPARAM][9];
+    if (cfg->use_default_params) default_params(P); else memcpy(P, cfg->params, sizeof(P));
+    for (int i = 0; i < MWB_NPARAM; i++)
+        for (int k = 0; k < 3; k++) { d.params[i].def[k] = P[i][k]; d.params[i].lo[k] = P[i][3 + k]; d.params[i].hi[k] = P[i][6 + k]; }
+    d.stk_cpf = 3;
+    // the environment's knobs
     { const char *dbg = getenv("MWB_DEBUG"); d.debug_flags = dbg ? atoi(dbg) : 0; }
     { const char *ex = getenv("MWB_EXP"); d.exp_flags = ex ? atoi(ex) : 0; }
-    d.tile_w = 0; d.tile_h = 0;
-    if (cfg->task >= MWB_TASK_PICKUPOBJS) {   // MWB_TILE=WxH (0x0: whole frames): the tile a workgroup renders in the entity tasks
-        int tw_ = 0, th_ = 0;   // default: whole frames (tiles cost 1.3 - 2.7x more in total: measured, scripts/ab_mesh_phases.py)
-        const char *tl = getenv("MWB_TILE");
-        if (tl && sscanf(tl, "%dx%d", &tw_, &th_) != 2) { tw_ = 0; th_ = 0; }
-        if (tw_ > 0 && th_ > 0) { d.tile_w = tw_ < cfg->obs_width ? tw_ : cfg->obs_width; d.tile_h = th_ < cfg->obs_height ? th_ : cfg->obs_height; }
-    }
-    static const double dflt[MWB_NUM_TASKS][4] = {{12, 0, 0, 0}, {10, 0, 0, 0}, {0, 0, 0, 0}, {8, 8, 3, 0}, {0, 0, 0, 0}, {0, 0, 0, 100}, {0, 0, 0, 0}, {0, 0, 0, 0}, {12, 0, 0, 0}, {0, 0, 0, 0},
-                                                 {12, 5, 0, 0}, {10, 0, 0, 0}, {16, 0, 0, 0}, {0, 0, 0, 0}, {10, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-    const bool sim2real = cfg->task == MWB_TASK_SIM2REAL_GOTO || cfg->task == MWB_TASK_SIM2REAL_PUSH;
-    const int task = cfg->task;
-    d.ent_task = task >= MWB_TASK_PICKUPOBJS ? 1 : 0;
-    d.n_boxes = (cfg->task == MWB_TASK_TMAZE_TWOBOX || cfg->task == MWB_TASK_SIM2REAL_PUSH) ? 2 : cfg->task == MWB_TASK_PUTNEXT ? 6 : 1;
-    if (task == MWB_TASK_PICKUPOBJS) {
-        const double no = cfg->task_args[1] != 0 ? cfg->task_args[1] : 5;
-        if (!(no >= 1 && no <= MWB_MAX_ENTS) || no != (double)(int)no) { delete h; return set_err(MWB_EINVAL, "PickupObjs: num_objs must be 1 .. 20"); }
-        d.n_boxes = (int)no;
-    } else if (task == MWB_TASK_ROOMOBJS) d.n_boxes = 3;
-    else if (task == MWB_TASK_COLLECTHEALTH) d.n_boxes = 18;
-    else if (task == MWB_TASK_THREEROOMS) d.n_boxes = 6;
-    else if (task == MWB_TASK_SIGN || task == MWB_TASK_SIDEWALK) d.n_boxes = 7;
-    else if (task == MWB_TASK_WALLGAP) d.n_boxes = 2;
-    d.frame_words = MWB_FRAME_WORDS_FOR(d.ent_task ? MWB_MAX_ENTS : d.n_boxes);   // the entity render kernels are compiled for every slot
-    d.n_tex = sim2real ? 17 : d.ent_task ? (task == MWB_TASK_SIGN ? MWB_NUM_TEXTURES : MWB_TEX_CHAR0) : 7;
+    { const char *no = getenv("MWB_NO_OVERLAP"); h->overlap_reset = !(no && atoi(no)); }
     {   // the last ~0.6 round of resident workgroups (5 per CU x 256 CUs = 1280) of a bulk render launch drains in
         // half-frame units: measured best between 640 and 960 envs (+4 % at 8192 Maze envs); MWB_SPLIT overrides
         const char *sp = getenv("MWB_SPLIT");
         int split = sp ? atoi(sp) : 768;
         d.split_envs = split < 0 ? 0 : (split > cfg->num_envs ? cfg->num_envs : split);
     }
-    d.no_ceiling = (sim2real || task == MWB_TASK_PICKUPOBJS || task == MWB_TASK_ROOMOBJS || task == MWB_TASK_SIDEWALK || task == MWB_TASK_WALLGAP) ? 1 : 0;
-    d.poly = cfg->task == MWB_TASK_YMAZE ? 1 : 0;
-    d.room_words = d.poly ? MWB_POLY_ROOM_WORDS : MWB_ROOM_WORDS;
-    d.agent_radius = sim2real ? 0.11 : task == MWB_TASK_ROOMOBJS ? 1.5 : 0.4;   // simtorealgoto.py:50 / roomobjs.py:36 / entity.py:451
-    for (int i = 0; i < 4; i++) d.task_args[i] = cfg->task_args[i] != 0 ? cfg->task_args[i] : dflt[cfg->task][i];
-    int mes = cfg->max_episode_steps;
-    if (mes <= 0) {   // hallway.py:18, oneroom.py:14, fourrooms.py:15, maze.py:27
-        if (d.task == MWB_TASK_HALLWAY) mes = 250;
-        else if (d.task == MWB_TASK_ONEROOM) mes = 180;
-        else if (d.task == MWB_TASK_FOURROOMS) mes = 250;
-        else if (d.task == MWB_TASK_TMAZE || d.task == MWB_TASK_TMAZE_TWOBOX) mes = 280;   // tmaze.py:20,142
-        else if (d.task == MWB_TASK_SIM2REAL_GOTO) mes = 100;   // simtorealgoto.py:30
-        else if (d.task == MWB_TASK_SIM2REAL_PUSH) mes = 150;   // simtorealpush.py:29
-        else if (d.task == MWB_TASK_PUTNEXT) mes = 250;   // putnext.py:16
-        else if (d.task == MWB_TASK_YMAZE) mes = 280;     // ymaze.py:21
-        else if (d.task == MWB_TASK_PICKUPOBJS) mes = 400;        // pickupobjs.py:19
-        else if (d.task == MWB_TASK_ROOMOBJS) mes = 2147483647;   // roomobjs.py:19: math.inf
-        else if (d.task == MWB_TASK_COLLECTHEALTH) mes = 1000;    // collecthealth.py:24
-        else if (d.task == MWB_TASK_THREEROOMS) mes = 400;        // threerooms.py:14
-        else if (d.task == MWB_TASK_SIGN) mes = 20;               // sign.py:41
-        else if (d.task == MWB_TASK_SIDEWALK) mes = 150;          // sidewalk.py:15
-        else if (d.task == MWB_TASK_WALLGAP) mes = 300;           // wallgap.py:14
-        else mes = (int)d.task_args[0] * (int)d.task_args[1] * 24;
+    if (d.ent_task) {   // MWB_TILE=WxH (0x0: whole frames): the tile a workgroup renders in the entity tasks
+        int tw_ = 0, th_ = 0;   // default: whole frames (tiles cost 1.3 - 2.7x more in total: measured, scripts/ab_mesh_phases.py)
+        const char *tl = getenv("MWB_TILE");
+        if (tl && sscanf(tl, "%dx%d", &tw_, &th_) != 2) { tw_ = 0; th_ = 0; }
+        if (tw_ > 0 && th_ > 0) { d.tile_w = tw_ < d.W ? tw_ : d.W; d.tile_h = th_ < d.H ? th_ : d.H; }
     }
-    d.max_episode_steps = mes;
-    double P[MWB_NPARAM][9];
-    if (cfg->use_default_params) default_params(P); else memcpy(P, cfg->params, sizeof(P));
-    for (int i = 0; i < MWB_NPARAM; i++)
-        for (int k = 0; k < 3; k++) { d.params[i].def[k] = P[i][k]; d.params[i].lo[k] = P[i][3 + k]; d.params[i].hi[k] = P[i][6 + k]; }
-    if (d.task == MWB_TASK_HALLWAY) { if (!(d.task_args[0] >= 2)) { delete h; return set_err(MWB_EINVAL, "Hallway: length >= 2"); } d.R_max = 1; d.S_max = 4; }
-    else if (d.task == MWB_TASK_ONEROOM) { if (!(d.task_args[0] >= 2)) { delete h; return set_err(MWB_EINVAL, "OneRoom: size >= 2"); } d.R_max = 1; d.S_max = 4; }
-    else if (d.task == MWB_TASK_FOURROOMS) { d.R_max = 8; d.S_max = 32; }
-    else if (d.task == MWB_TASK_TMAZE || d.task == MWB_TASK_TMAZE_TWOBOX) {
-        if (d.task_args[3] < 0 || d.task_args[3] > 9e15) { delete h; return set_err(MWB_EINVAL, "TMaze: bad sub_task_length"); }
-        d.R_max = 2; d.S_max = 8;
-    } else if (sim2real) { d.R_max = 1; d.S_max = 4; }
-    else if (d.task == MWB_TASK_YMAZE) { d.R_max = 6; d.S_max = 24; }   // corridor, hub, two arms, two connectors (the third pair of portals meets directly)
-    else if (d.task == MWB_TASK_PUTNEXT) { if (!(d.task_args[0] >= 2)) { delete h; return set_err(MWB_EINVAL, "PutNext: size >= 2"); } d.R_max = 1; d.S_max = 4; }
-    else if (d.task == MWB_TASK_PICKUPOBJS || d.task == MWB_TASK_ROOMOBJS || d.task == MWB_TASK_COLLECTHEALTH) {
-        if (!(d.task_args[0] >= 2)) { delete h; return set_err(MWB_EINVAL, "size >= 2"); }
-        d.R_max = 1; d.S_max = 4;
-    } else if (d.ent_task) {
-        if (d.task == MWB_TASK_SIGN && (d.task_args[0] != 10 || d.task_args[1] < 0 || d.task_args[1] > 2 || d.task_args[2] < 0 || d.task_args[2] > 1 ||
-                                        d.task_args[1] != (double)(int)d.task_args[1] || d.task_args[2] != (double)(int)d.task_args[2])) {
-            delete h;   // the objects sit at fixed coordinates (sign.py:91-102): only the default room fits them
-            return set_err(MWB_EINVAL, "Sign: size must be 10, color_index 0..2, goal 0..1");
-        }
-        d.R_max = 8; d.S_max = 24;
+    // an observation that does not fit one workgroup's LDS (or its 16-bit pixel queue) is rendered in tiles, like mwb_render_view's frames
+    if (d.tile_w == 0 && (mwb_render_lds_bytes(d) > 160 * 1024 || !mwb_pixel_queue_fits(d.W, d.H))) {
+        int tw = 0, th = 0;
+        mwb_view_tile(&tw, &th);
+        d.tile_w = tw < d.W ? tw : d.W; d.tile_h = th < d.H ? th : d.H;
     }
-    else {
-        int rows = (int)d.task_args[0], cols = (int)d.task_args[1];
-        if (rows < 1 || cols < 1 || rows * cols > 4096) { delete h; return set_err(MWB_EINVAL, "Maze: bad num_rows / num_cols"); }
-        d.R_max = 2 * rows * cols - 1; d.S_max = 4 * rows * cols;
-        if (d.S_max < 8) d.S_max = 8;
-    }
-    size_t N = (size_t)d.N;
+    // last-frame reuse: N x (W*H*3 [+ W*H*4 with depth]) bytes of cache and two flags per env; MWB_NO_FRAME_REUSE=1 turns it off
+    { const char *no = getenv("MWB_NO_FRAME_REUSE"); h->frame_reuse = !(no && atoi(no)) && d.tile_w == 0; }
+
+    // device memory: the per-env arrays from their list (mwb_internal.h), then what is not per env
+    const size_t N = (size_t)d.N;
     int rc = MWB_OK;
-#define A(ptr, n) if (rc == MWB_OK) rc = dev_alloc(h, &(ptr), (n))
-    A(d.agent_x, N); A(d.agent_z, N); A(d.agent_dir, N); A(d.box_x, N * d.n_boxes); A(d.box_z, N * d.n_boxes); A(d.box_y, N * d.n_boxes); A(d.box_dir, N * d.n_boxes); A(d.carrying, N);
-    A(d.box_color, N * d.n_boxes * 3); A(d.box_size, N * d.n_boxes); A(d.goal_dist, N); A(d.episode_count, N); A(d.task_step_count, N); A(d.goal_idx, N); A(d.cam, N * 4); A(d.sky_color, N * 3); A(d.light_pos, N * 3); A(d.light_color, N * 3); A(d.light_ambient, N * 3);
-    A(d.step_count, N); A(d.n_rooms, N); A(d.n_rrooms, N); A(d.seg_stage, (size_t)MWB_RESET_MAX_BLOCKS * d.S_max * 4); A(d.n_segs, N); A(d.reset_set, N); A(d.reset_list, N); A(d.reset_count, (size_t)1);
-    if (d.ent_task) {
-        A(d.ent_meta, N * d.n_boxes); A(d.ent_radius, N * d.n_boxes); A(d.ent_height, N * d.n_boxes); A(d.ent_scale, N * d.n_boxes);
-        A(d.ent_order, N * MWB_ORDER_STRIDE); A(d.n_order, N); A(d.task_f, N); A(d.task_i, N); A(d.text_tex, N * 8);
-        A(d.ovr_slot, N); A(d.ovr_pose, N * 4);
-        A(h->mesh_desc_dev, (size_t)MWB_NUM_MESHES);
-    }
-    A(d.rng, N * MWB_MT_WORDS); A(d.rooms, N * d.R_max * d.room_words); A(d.segs, N * d.S_max * 4); A(d.frame, N * d.frame_words); A(d.world_ext, N * 4);
-    A(d.obs, N * d.W * d.H * 3);
-    if (d.want_depth) { A(d.depth, N * d.W * d.H); }
+    mwb_for_each_env_array(d, d, h->frame_reuse, [&](auto *&, auto *&p, const MwbEnvArray &a) {
+        if (rc == MWB_OK) rc = dev_alloc(h, &p, mwb_env_array_elems(a, N));
+    });
+#define A(ptr, n) if (rc == MWB_OK) rc = dev_alloc(h, &(ptr), (size_t)(n))
+    A(d.seg_stage, (size_t)MWB_RESET_MAX_BLOCKS * d.S_max * 4);
+    A(d.reset_count, 1); A(d.error_flag, 1); A(d.order_state, 2); A(d.list_counts, 2); A(d.reuse_stats, 2);
+    if (d.debug_flags & 16) { A(d.wg_ts, 2 * (N + (size_t)d.split_envs)); }
+    if (d.exp_flags & 4) { A(d.dbg_counters, 8); }
     {   // the small per-step outputs share one allocation (one D2H copy for a host-side consumer); 16-byte aligned parts
         auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
         // ordered by how often a host-side consumer needs them, so that it can copy a PREFIX: done | reward (what every step of a
@@ -359,52 +312,27 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
             d.feature = (float *)(pack + o_feat); d.ep_steps = (int32_t *)(pack + o_eps); d.done = pack + o_done;
         }
     }
-    A(h->tex_desc_dev, (size_t)MWB_MAX_TEX);
-    A(h->scratch_int_dev, (size_t)4);
-    A(d.error_flag, (size_t)1);
+    A(h->tex_desc_dev, MWB_MAX_TEX);
+    if (d.ent_task) { A(h->mesh_desc_dev, MWB_NUM_MESHES); }
+    A(h->scratch_int_dev, 4);
     A(h->rep_sum, N); A(h->rep_taken, N); A(h->rep_same, N); A(h->rep_frozen, N);
 #undef A
-    if (rc == MWB_OK && (d.debug_flags & 16)) rc = dev_alloc(h, &d.wg_ts, 2 * (N + (size_t)d.split_envs));
-    if (rc == MWB_OK && (d.exp_flags & 4)) rc = dev_alloc(h, &d.dbg_counters, (size_t)8);
-    if (rc == MWB_OK) rc = dev_alloc(h, &d.cost, 2 * N);
-    if (rc == MWB_OK) rc = dev_alloc(h, &d.bucket, N);
-    if (rc == MWB_OK) rc = dev_alloc(h, &d.order_bufs[0], N);
-    if (rc == MWB_OK) rc = dev_alloc(h, &d.order_bufs[1], N);
-    if (rc == MWB_OK) rc = dev_alloc(h, &d.order_state, (size_t)2);
-    if (rc == MWB_OK) rc = dev_alloc(h, &d.render_list, N);
-    if (rc == MWB_OK) rc = dev_alloc(h, &d.reuse_list, N);
-    if (rc == MWB_OK) rc = dev_alloc(h, &d.list_counts, (size_t)2);
+    d.tex_desc = h->tex_desc_dev; d.mesh_desc = h->mesh_desc_dev;
     if (rc == MWB_OK) {   // no cost known yet: identity order
         std::vector<int32_t> ident(N);
         for (size_t i = 0; i < N; i++) ident[i] = (int32_t)i;
         for (int k = 0; k < 2 && rc == MWB_OK; k++)
             if (hipMemcpy(d.order_bufs[k], ident.data(), N * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) rc = set_err(MWB_EHIP, "mwb_create: hipMemcpy failed");
     }
-    if (rc != MWB_OK) { mwb_destroy(h); return rc; }
     // MiniWorldEnv.__init__ ends with self.reset() (miniworld.py:523): the episode counters of TMazeDynamic /
     // TMazeTwoBoxDynamic (tmaze.py:80,130) have seen one reset when the caller gets the env
-    if ((d.task == MWB_TASK_TMAZE && d.task_args[3] > 0) || (d.task == MWB_TASK_TMAZE_TWOBOX && d.task_args[0] == 0)) {
+    if (rc == MWB_OK && ((d.task == MWB_TASK_TMAZE && d.task_args[3] > 0) || (d.task == MWB_TASK_TMAZE_TWOBOX && d.task_args[0] == 0))) {
         std::vector<int64_t> ones(N, 1);
-        if (hipMemcpy(d.episode_count, ones.data(), N * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) {
-            mwb_destroy(h);
-            return set_err(MWB_EHIP, "mwb_create: hipMemcpy failed");
-        }
+        if (hipMemcpy(d.episode_count, ones.data(), N * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess) rc = set_err(MWB_EHIP, "mwb_create: hipMemcpy failed");
     }
-    if (hipMemset(d.carrying, 0xFF, N * sizeof(int32_t)) != hipSuccess) { mwb_destroy(h); return set_err(MWB_EHIP, "mwb_create: hipMemset failed"); }   // -1: nothing carried
-    d.tex_desc = h->tex_desc_dev;
-    h->texels_dev = nullptr; d.texels = nullptr;
-    h->seeded = false; h->textures_dirty = false; h->have_textures = false; h->have_obs = false;
-    h->timing = false; h->timing_now = false; h->timing_period = 1; h->timing_tick = 0; h->ev_used = 0; h->ev = nullptr;
-    { const char *no = getenv("MWB_NO_OVERLAP"); h->overlap_reset = !(no && atoi(no)); }
-    h->side = nullptr; h->ev_fork = nullptr; h->ev_join = nullptr;
-    h->view_frame = nullptr;
-    h->serial = g_next_serial++; h->have_world = false;
-    h->copy_dst_pairs = nullptr; h->copy_src_mark = nullptr; h->copy_pairs = nullptr; h->copy_pairs_cap = 0; h->copy_rejected = nullptr;
-    h->copy_tables = nullptr; h->copy_table_next = 0;
-    for (auto &t : h->copy_table) { t.src = 0; t.n_small = 0; t.small_chunks = 0; t.n_large = 0; }
-    h->meshes_dirty = false; h->mesh_data_dev = nullptr; d.mesh_desc = h->mesh_desc_dev; d.mesh_data = nullptr;
-    h->stack = nullptr; h->stack_n = 0; h->stack_dtype = 0; h->stack_bytes = 0; h->stack_planes = 0; h->stack_pos = 0; h->stack_fused = 0;
-    h->stack_cpf = 3; d.stk_cpf = 3; h->grey_bytes = 0;
+    if (rc == MWB_OK && hipMemset(d.carrying, 0xFF, N * sizeof(int32_t)) != hipSuccess) rc = set_err(MWB_EHIP, "mwb_create: hipMemset failed");   // -1: nothing carried
+    if (rc != MWB_OK) { mwb_destroy(h); return rc; }
+
     int prio_lo = 0, prio_hi = 0;
     hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);   // numerically lowest = highest priority
     if (hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, prio_hi) != hipSuccess ||
@@ -413,23 +341,6 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
         mwb_destroy(h);
         return set_err(MWB_EHIP, "mwb_create: could not create the side stream / events");
     }
-    for (int i = 0; i < MWB_MAX_TEX; i++) { h->tex_w[i] = 0; h->tex_h[i] = 0; }
-    // an observation that does not fit one workgroup's LDS (or its 16-bit pixel queue) is rendered in tiles, like mwb_render_view's frames
-    if (d.tile_w == 0 && (mwb_render_lds_bytes(d) > 160 * 1024 || !mwb_pixel_queue_fits(d.W, d.H))) {
-        int tw = 0, th = 0;
-        mwb_view_tile(&tw, &th);
-        d.tile_w = tw < d.W ? tw : d.W; d.tile_h = th < d.H ? th : d.H;
-    }
-    // last-frame reuse: N x (W*H*3 [+ W*H*4 with depth]) bytes of cache and two flags per env; MWB_NO_FRAME_REUSE=1 turns it off
-    { const char *no = getenv("MWB_NO_FRAME_REUSE"); h->frame_reuse = !(no && atoi(no)) && d.tile_w == 0; }
-    rc = dev_alloc(h, &d.reuse_stats, (size_t)2);
-    if (rc == MWB_OK && h->frame_reuse) {
-        rc = dev_alloc(h, &d.frame_cache, N * d.W * d.H * 3);
-        if (rc == MWB_OK && d.want_depth) rc = dev_alloc(h, &d.depth_cache, N * d.W * d.H);
-        if (rc == MWB_OK) rc = dev_alloc(h, &d.frame_cached, N);
-        if (rc == MWB_OK) rc = dev_alloc(h, &d.frame_same, N);
-    }
-    if (rc != MWB_OK) { mwb_destroy(h); return rc; }
     if (int prc = mwb_prepare_kernels(d)) {
         mwb_destroy(h);
         return set_err(prc == -2 ? MWB_EHIP : MWB_EINVAL,
@@ -558,25 +469,10 @@ extern "C" int mwb_set_mesh_dims(mwb_handle *h, int geom, double height, double 
     return MWB_OK;
 }
 
-// which geometries (and (geometry, height) pairs) the task builds
-static const int *task_meshes(int task, int *n) {
-    static const int pick[2] = {MWB_MESH_BALL, MWB_MESH_KEY}, health[1] = {MWB_MESH_MEDKIT}, three[3] = {MWB_MESH_DUCKIE, MWB_MESH_KEY, MWB_MESH_BALL},
-                     sign[1] = {MWB_MESH_KEY}, side[2] = {MWB_MESH_BUILDING, MWB_MESH_CONE}, gap[1] = {MWB_MESH_BUILDING};
-    switch (task) {
-    case MWB_TASK_PICKUPOBJS: case MWB_TASK_ROOMOBJS: *n = 2; return pick;
-    case MWB_TASK_COLLECTHEALTH: *n = 1; return health;
-    case MWB_TASK_THREEROOMS: *n = 3; return three;
-    case MWB_TASK_SIGN: *n = 1; return sign;
-    case MWB_TASK_SIDEWALK: *n = 2; return side;
-    case MWB_TASK_WALLGAP: *n = 1; return gap;
-    }
-    *n = 0; return nullptr;
-}
-
 static int upload_meshes(mwb_handle *h) {   // the caller holds the device guard
-    int n_need = 0;
-    const int *need = task_meshes(h->dev.task, &n_need);
-    for (int k = 0; k < n_need; k++) {
+    const MwbTaskRow &row = MWB_TASK_TABLE[h->dev.task];
+    const int *need = row.meshes;
+    for (int k = 0; k < row.n_meshes; k++) {
         if (!h->meshes[need[k]].set) return set_err(MWB_ESTATE, "reset / render requested before the task's meshes were set (mwb_set_mesh)");
         bool dims = false;
         for (int q = 0; q < h->dev.n_mesh_dims; q++) dims = dims || h->dev.mesh_dims[q].geom == need[k];
@@ -1005,7 +901,7 @@ static int copy_table_for(mwb_handle *dst, mwb_handle *src) {
         if (dst->copy_table[k].src == src->serial) return k;
     std::vector<MwbCopyDesc> small, large;
     uint32_t chunks = 0;
-    mwb_for_each_env_array(src->dev, dst->dev, [&](const char *s, char *d, uint32_t rows, uint32_t elem, uint64_t ss, uint64_t ds) {
+    mwb_for_each_copied_array(src->dev, dst->dev, [&](const char *s, char *d, uint32_t rows, uint32_t elem, uint64_t ss, uint64_t ds) {
         MwbCopyDesc t;
         t.src = s; t.dst = d; t.rows = rows; t.elem = elem; t.src_stride = ss; t.dst_stride = ds; t.first_chunk = 0; t.pad = 0;
         if (elem <= MWB_COPY_SMALL_ELEM) { t.first_chunk = chunks; chunks += (rows + MWB_COPY_ROW_CHUNK - 1) / MWB_COPY_ROW_CHUNK; small.push_back(t); }
@@ -1113,7 +1009,7 @@ extern "C" long long mwb_copy_env_bytes(mwb_handle *dst, mwb_handle *src) {
     if (const char *f = config_difference(dst, src))
         return set_err(MWB_EINVAL, std::string("mwb_copy_env_bytes: the handles' configurations differ in `") + f + "`");
     size_t total = 0;
-    mwb_for_each_env_array(src->dev, dst->dev, [&](const char *, char *, uint32_t rows, uint32_t elem, uint64_t, uint64_t) { total += (size_t)rows * elem; });
+    mwb_for_each_copied_array(src->dev, dst->dev, [&](const char *, char *, uint32_t rows, uint32_t elem, uint64_t, uint64_t) { total += (size_t)rows * elem; });
     return (long long)total;
 }
 

@@ -4,7 +4,7 @@
 //   copy_validate_kernel  the only code that reads the caller's index lists.  Three launches (the passes of mwb_copy_check.h)
 //                         leave one int2 {dst, src} per pair, dst = -1 where the pair is not carried out; everything below
 //                         reads these and nothing else, so no index reaches an address computation unchecked.
-//   copy_envs_kernel      the per-env arrays of MwbDev through the descriptor table (mwb_for_each_env_array, mwb_internal.h).
+//   copy_envs_kernel      the per-env arrays of MwbDev through the descriptor table (mwb_for_each_copied_array, mwb_internal.h).
 //                         <false>: pieces of up to 32 bytes, lane = pair, one workgroup per chunk of rows of one array - with
 //                         consecutive destination (and source) indices, the common arange list, a wave moves one contiguous
 //                         run of 64 pieces.  <true>: large env-major rows (the MT19937 state, the room table), one workgroup

@@ -235,16 +235,71 @@ struct MwbDev {
     const uint8_t *frozen;  // [N]
 };
 
-// ---- mwb_copy_envs: every per-env array of MwbDev that a later kernel READS as state, in one place.  An array added to the
-// struct above that carries state from one pass to the next must be added here too, or a copied env is no twin of its source.
-// Not listed on purpose: `frame` (prep rebuilds it before every render), cost / bucket / order_bufs (a dispatch heuristic), the
-// outputs of the last transition (reward, reward64, done, ep_steps, feature, goal_pos: the next step rewrites them), reset_set /
-// reset_list / frame_cached / frame_same and the frame caches (the copy pass and the render it runs maintain them), seg_stage
-// (scratch of one reset_kernel launch).
-// One descriptor per array: env e of the array is `rows` pieces of `elem` bytes, piece r at base + r * row_stride + e * elem.
-// An env-major block (rng [N][625], rooms [N][R_max][words], cam [N][4] ...) is one row of many bytes; an env-minor array
-// (agent_x [N], box_x [B][N], box_color [B][N][3], segs [S_max][4][N]) is many rows N * elem apart - N differs between two
-// handles, so both strides travel.
+// ---- the per-env device arrays of MwbDev, each written down ONCE: mwb_create allocates from this list, mwb_copy_envs builds its
+// descriptor table from it and mwb_copy_env_bytes sums it.  A new array is one new line here (and its member above), no second
+// edit elsewhere; the line says whether a copied env needs it, so that an array which carries state from one pass to the next
+// cannot be left out of the copy unnoticed - a copied env would be no twin of its source.
+// Shapes: env-minor [rows][N][per] (agent_x [N], box_x [B][N], box_color [B][N][3], segs [S_max * 4][N]: one-env-per-lane reads
+// coalesce) or env-major [N][count] (rng [N][625], rooms [N][R_max * words], cam [N][4]).
+// Not per-env arrays, allocated by explicit lines in mwb_create: seg_stage (one row set per block of reset_kernel, scratch of one
+// launch), error_flag, reset_count, order_state, list_counts, reuse_stats, wg_ts, dbg_counters, the texture and mesh descriptors,
+// and the small outputs reward / reward64 / done / ep_steps / feature / goal_pos, which are parts of one allocation (`pack`).
+struct MwbEnvArray {
+    const char *name;
+    bool minor;               // env-minor [rows][N][per]; otherwise env-major [N][per], rows == 1
+    uint32_t rows;
+    size_t per;
+    const char *not_copied;   // null: state a later kernel reads, mwb_copy_envs copies it; otherwise why a copied env does without
+};
+static inline size_t mwb_env_array_elems(const MwbEnvArray &a, size_t N) { return N * a.rows * a.per; }   // what mwb_create allocates
+
+// f(s.member, d.member, MwbEnvArray) for every array that exists in handles of s's configuration; s and d differ in N at most
+// (mwb_create passes its one MwbDev twice).  frame_reuse: the handle keeps the last-frame cache.
+template <class Dev, class F>
+static inline void mwb_for_each_env_array(Dev &s, Dev &d, bool frame_reuse, F &&f) {
+#define MWB_MINOR(p, rows, per, when, why) if (when) f(s.p, d.p, MwbEnvArray{#p, true, (uint32_t)(rows), (size_t)(per), why})
+#define MWB_MAJOR(p, count, when, why) if (when) f(s.p, d.p, MwbEnvArray{#p, false, 1u, (size_t)(count), why})
+    const char *const COPIED = nullptr;
+    const char *const OUTPUT = "an output of the last transition or render: the next one rewrites it";
+    const char *const DISPATCH = "dispatch scratch: a heuristic or a work list rebuilt before every launch";
+    const char *const CACHE = "the copy pass and the render it runs maintain the cached frames and their flags";
+    const int B = s.n_boxes;
+    const bool always = true, ent = s.ent_task != 0, depth = s.want_depth != 0;
+    const size_t pixels = (size_t)s.W * s.H;
+    MWB_MINOR(agent_x, 1, 1, always, COPIED); MWB_MINOR(agent_z, 1, 1, always, COPIED); MWB_MINOR(agent_dir, 1, 1, always, COPIED);
+    MWB_MINOR(box_x, B, 1, always, COPIED); MWB_MINOR(box_z, B, 1, always, COPIED); MWB_MINOR(box_dir, B, 1, always, COPIED);
+    MWB_MINOR(box_y, B, 1, always, COPIED); MWB_MINOR(box_color, B, 3, always, COPIED); MWB_MINOR(box_size, B, 1, always, COPIED);
+    MWB_MINOR(carrying, 1, 1, always, COPIED); MWB_MINOR(goal_dist, 1, 1, always, COPIED);
+    MWB_MINOR(episode_count, 1, 1, always, COPIED); MWB_MINOR(task_step_count, 1, 1, always, COPIED); MWB_MINOR(goal_idx, 1, 1, always, COPIED);
+    MWB_MAJOR(cam, 4, always, COPIED); MWB_MAJOR(sky_color, 3, always, COPIED); MWB_MAJOR(light_pos, 3, always, COPIED);
+    MWB_MAJOR(light_color, 3, always, COPIED); MWB_MAJOR(light_ambient, 3, always, COPIED);
+    MWB_MINOR(step_count, 1, 1, always, COPIED); MWB_MINOR(n_rooms, 1, 1, always, COPIED); MWB_MINOR(n_segs, 1, 1, always, COPIED);
+    MWB_MINOR(n_rrooms, 1, 1, always, COPIED);
+    MWB_MAJOR(world_ext, 4, always, COPIED);
+    MWB_MAJOR(rng, MWB_MT_WORDS, always, COPIED);
+    MWB_MAJOR(rooms, (size_t)s.R_max * s.room_words, always, COPIED);
+    MWB_MINOR(segs, s.S_max * 4, 1, always, COPIED);
+    MWB_MINOR(ent_meta, B, 1, ent, COPIED); MWB_MINOR(ent_radius, B, 1, ent, COPIED); MWB_MINOR(ent_height, B, 1, ent, COPIED);
+    MWB_MINOR(ent_scale, B, 1, ent, COPIED);
+    MWB_MAJOR(ent_order, MWB_ORDER_STRIDE, ent, COPIED); MWB_MINOR(n_order, 1, 1, ent, COPIED);
+    MWB_MINOR(task_f, 1, 1, ent, COPIED); MWB_MINOR(task_i, 1, 1, ent, COPIED); MWB_MAJOR(text_tex, 8, ent, COPIED);
+    MWB_MINOR(ovr_slot, 1, 1, ent, COPIED); MWB_MAJOR(ovr_pose, 4, ent, COPIED);
+    MWB_MAJOR(frame, s.frame_words, always, "prep_kernel rebuilds it before every render");
+    MWB_MINOR(reset_set, 1, 1, always, "the copy pass sets and clears it around the render it runs");
+    MWB_MINOR(reset_list, 1, 1, always, "the copy pass sets and clears it around the render it runs");
+    MWB_MAJOR(obs, pixels * 3, always, OUTPUT); MWB_MAJOR(depth, pixels, depth, OUTPUT);
+    MWB_MAJOR(cost, 2, always, DISPATCH); MWB_MINOR(bucket, 1, 1, always, DISPATCH);
+    MWB_MINOR(order_bufs[0], 1, 1, always, DISPATCH); MWB_MINOR(order_bufs[1], 1, 1, always, DISPATCH);
+    MWB_MINOR(render_list, 1, 1, always, DISPATCH); MWB_MINOR(reuse_list, 1, 1, always, DISPATCH);
+    MWB_MAJOR(frame_cache, pixels * 3, frame_reuse, CACHE); MWB_MAJOR(depth_cache, pixels, frame_reuse && depth, CACHE);
+    MWB_MINOR(frame_cached, 1, 1, frame_reuse, CACHE); MWB_MINOR(frame_same, 1, 1, frame_reuse, CACHE);
+#undef MWB_MINOR
+#undef MWB_MAJOR
+}
+
+// ---- mwb_copy_envs.  One descriptor per copied array: env e of the array is `rows` pieces of `elem` bytes, piece r at
+// base + r * row_stride + e * elem.  An env-major block is one row of many bytes; an env-minor array is many rows N * elem
+// apart - N differs between two handles, so both strides travel.
 struct MwbCopyDesc {
     const char *src;
     char *dst;
@@ -256,32 +311,14 @@ struct MwbCopyDesc {
 #define MWB_COPY_SMALL_ELEM 32   // pieces up to this size are copied one per lane (lane = pair); larger ones by a workgroup per pair
 #define MWB_COPY_ROW_CHUNK 8     // rows of one small array a workgroup of copy_envs_kernel takes
 
-// f(src base, dst base, rows, elem bytes, src row stride, dst row stride) for every array; s and d of equal configuration but N
+// f(src base, dst base, rows, elem bytes, src row stride, dst row stride) for every array of the list that a copy moves
 template <class F>
-static inline void mwb_for_each_env_array(const MwbDev &s, const MwbDev &d, F &&f) {
-#define MWB_MINOR(p, rows, per) f((const char *)s.p, (char *)d.p, (uint32_t)(rows), (uint32_t)(sizeof(*s.p) * (per)), \
-                                  (uint64_t)sizeof(*s.p) * (per) * (uint64_t)s.N, (uint64_t)sizeof(*s.p) * (per) * (uint64_t)d.N)
-#define MWB_MAJOR(p, count) f((const char *)s.p, (char *)d.p, 1u, (uint32_t)(sizeof(*s.p) * (count)), (uint64_t)0, (uint64_t)0)
-    const int B = s.n_boxes;
-    MWB_MINOR(agent_x, 1, 1); MWB_MINOR(agent_z, 1, 1); MWB_MINOR(agent_dir, 1, 1);
-    MWB_MINOR(box_x, B, 1); MWB_MINOR(box_z, B, 1); MWB_MINOR(box_dir, B, 1); MWB_MINOR(box_y, B, 1);
-    MWB_MINOR(box_color, B, 3); MWB_MINOR(box_size, B, 1);
-    MWB_MINOR(carrying, 1, 1); MWB_MINOR(goal_dist, 1, 1);
-    MWB_MINOR(episode_count, 1, 1); MWB_MINOR(task_step_count, 1, 1); MWB_MINOR(goal_idx, 1, 1);
-    MWB_MAJOR(cam, 4); MWB_MAJOR(sky_color, 3); MWB_MAJOR(light_pos, 3); MWB_MAJOR(light_color, 3); MWB_MAJOR(light_ambient, 3);
-    MWB_MINOR(step_count, 1, 1); MWB_MINOR(n_rooms, 1, 1); MWB_MINOR(n_segs, 1, 1); MWB_MINOR(n_rrooms, 1, 1);
-    MWB_MAJOR(world_ext, 4);
-    MWB_MAJOR(rng, MWB_MT_WORDS);
-    MWB_MAJOR(rooms, (size_t)s.R_max * s.room_words);
-    MWB_MINOR(segs, s.S_max * 4, 1);
-    if (s.ent_task) {
-        MWB_MINOR(ent_meta, B, 1); MWB_MINOR(ent_radius, B, 1); MWB_MINOR(ent_height, B, 1); MWB_MINOR(ent_scale, B, 1);
-        MWB_MAJOR(ent_order, MWB_ORDER_STRIDE); MWB_MINOR(n_order, 1, 1);
-        MWB_MINOR(task_f, 1, 1); MWB_MINOR(task_i, 1, 1); MWB_MAJOR(text_tex, 8);
-        MWB_MINOR(ovr_slot, 1, 1); MWB_MAJOR(ovr_pose, 4);
-    }
-#undef MWB_MINOR
-#undef MWB_MAJOR
+static inline void mwb_for_each_copied_array(const MwbDev &s, const MwbDev &d, F &&f) {
+    mwb_for_each_env_array(s, d, false, [&](auto *sp, auto *dp, const MwbEnvArray &a) {   // (no array behind frame_reuse is copied)
+        if (a.not_copied) return;
+        const uint64_t elem = sizeof(*sp) * a.per;
+        f((const char *)sp, (char *)dp, a.rows, (uint32_t)elem, a.minor ? elem * (uint64_t)s.N : 0, a.minor ? elem * (uint64_t)d.N : 0);
+    });
 }
 
 // launch wrappers implemented in mwb_copy.hip (mwb_copy_envs).  `pairs`: per pair of the call {dst, src} as copy_validate_kernel
