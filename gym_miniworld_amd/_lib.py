@@ -30,6 +30,7 @@ TEX_MESH0, TEX_CHAR0 = 21, 25
 LAYOUT_HWC, LAYOUT_CWH = 0, 1
 COPY_NO_RENDER = 1   # MWB_COPY_NO_RENDER
 MAX_REPEAT = 64      # MWB_MAX_REPEAT
+ROLLOUT_GREY = 1     # MWB_ROLLOUT_GREY
 
 
 class MwbConfig(ctypes.Structure):
@@ -62,6 +63,17 @@ class MwbState(ctypes.Structure):
         "ent_meta", "ent_radius", "ent_height", "ent_scale", "ent_order", "task_f", "task_i", "text_tex")]
 
 
+class MwbRolloutInfo(ctypes.Structure):   # struct mwb_rollout_info
+    _fields_ = [
+        ("reward", ctypes.c_void_p), ("mask", ctypes.c_void_p), ("feature", ctypes.c_void_p), ("age", ctypes.c_void_p),
+        ("ring", ctypes.c_void_p),
+        ("reward_bytes", ctypes.c_size_t), ("mask_bytes", ctypes.c_size_t), ("feature_bytes", ctypes.c_size_t),
+        ("age_bytes", ctypes.c_size_t), ("ring_bytes", ctypes.c_size_t),
+        ("num_steps", ctypes.c_int32), ("nstack", ctypes.c_int32), ("grey", ctypes.c_int32), ("cursor", ctypes.c_int32),
+        ("base", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+
 EXPORTS = [
     "mwb_create", "mwb_destroy", "mwb_last_error", "mwb_abi_version", "mwb_set_texture", "mwb_seed", "mwb_reset",
     "mwb_step", "mwb_render", "mwb_get_outputs", "mwb_get_state", "mwb_set_agent", "mwb_intersect",
@@ -71,6 +83,7 @@ EXPORTS = [
     "mwb_grey_enable", "mwb_grey_output", "mwb_grey_convert",
     "mwb_copy_envs", "mwb_copy_rejected", "mwb_copy_env_bytes",
     "mwb_step_repeat", "mwb_repeat_taken",
+    "mwb_rollout_enable", "mwb_rollout_push", "mwb_rollout_gather", "mwb_rollout_after_update", "mwb_rollout_info", "mwb_rollout_rejected",
 ]
 
 _lib = None
@@ -136,7 +149,13 @@ def load():
     L.mwb_copy_rejected.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
     L.mwb_copy_env_bytes.argtypes = [vp, vp]
     L.mwb_copy_env_bytes.restype = ctypes.c_longlong
-    L.mwb_timing_read.argtypes = [vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(i32)]
+    L.mwb_rollout_enable.argtypes = [vp, i32, i32, ctypes.c_uint]
+    L.mwb_rollout_push.argtypes = [vp, i32, vp, vp]
+    L.mwb_rollout_gather.argtypes = [vp, vp, i32, vp, i32, vp]
+    L.mwb_rollout_after_update.argtypes = [vp, vp]
+    L.mwb_rollout_info.argtypes = [vp, ctypes.POINTER(MwbRolloutInfo)]
+    L.mwb_rollout_rejected.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
+    L.mwb_timing_read.argtypes = [vp] +[ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(i32)]
     if L.mwb_abi_version() != ABI_VERSION:
         raise MwbError("libmwbatch.so ABI version mismatch")
     _lib = L

@@ -128,6 +128,116 @@ def check_repeat_args(repeat, num_envs, n_actions, n_skip=None, n_counts=None, n
     return int(repeat)
 
 
+def check_rollout_indices(index, cursor, num_envs):
+    """What Rollout.gather refuses before anything is launched, for an index list that lives on the host: raises ValueError for
+    an empty list, for indices that are no integers and for an index outside [0, (cursor + 1) * num_envs) - a row the device
+    would write as zeros and count (mwb_rollout_rejected).  index[i] = t * num_envs + e, t in 0 .. cursor.  Returns the list as
+    a one-dimensional int64 array."""
+    a = np.asarray(index)
+    if a.size == 0:
+        raise ValueError("rollout gather: the index list is empty")
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("rollout gather: indices must be integers, not %s" % a.dtype)
+    a = a.reshape(-1).astype(np.int64)
+    if (a < 0).any():
+        raise ValueError("rollout gather: negative index %d" % a[a < 0][0])
+    limit = (int(cursor) + 1) * int(num_envs)
+    if (a >= limit).any():
+        raise ValueError("rollout gather: index %d outside [0, %d) = (cursor + 1) * num_envs with the cursor at %d"
+                         % (a[a >= limit][0], limit, cursor))
+    return a
+
+
+class Rollout:
+    """The observation half of RolloutStorage (pytorch-a2c-ppo-acktr/storage.py) on the device, every frame stored once
+    (BatchedMiniWorld.rollout_enable; include/miniworld_batch.h at mwb_rollout_enable):
+        ro.push(after_reset=True) after reset(), ro.push() after every step()     rollouts.obs[step + 1].copy_(obs) + insert()
+        ro.gather(idx)                                                            obs[:-1].view(-1, ...)[idx]
+        ro.after_update()                                                         rollouts.after_update()
+    rewards [T, N], masks [T+1, N], features [T+1, N, 2] and ages [T+1, N] are zero-copy views of the library's arrays."""
+
+    def __init__(self, batch, num_steps, nstack, grey):
+        torch = batch.torch
+        self.batch, self.L, self.torch = batch, batch.L, torch
+        _lib.check(self.L.mwb_rollout_enable(batch.h, int(num_steps), int(nstack), _lib.ROLLOUT_GREY if grey else 0))
+        info = self._info()
+        N = batch.num_envs
+        self.num_steps, self.nstack, self.grey, self.num_envs = int(info.num_steps), int(info.nstack), bool(info.grey), N
+        self.channels = self.nstack * (1 if self.grey else 3)
+        self.nbytes = int(info.ring_bytes + info.reward_bytes + info.mask_bytes + info.feature_bytes + info.age_bytes)
+        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, batch), device=batch.device)  # noqa: E731
+        T = self.num_steps
+        self.rewards = as_t(info.reward, (T, N), "<f4")
+        self.masks = as_t(info.mask, (T + 1, N), "<f4")
+        self.features = as_t(info.feature, (T + 1, N, 2), "<f4")
+        self.ages = as_t(info.age, (T + 1, N), "|u1")
+        self._arange = torch.arange(N, dtype=torch.int64, device=batch.device)
+        self._keep = None
+
+    def _info(self):
+        info = _lib.MwbRolloutInfo()
+        _lib.check(self.L.mwb_rollout_info(self.batch.h, ctypes.byref(info)))
+        return info
+
+    @property
+    def step(self):
+        """the cursor: the last logical time pushed (0 after the reset push and after after_update; -1 before the first push)"""
+        return int(self._info().cursor)
+
+    @property
+    def full(self):
+        return self.step >= self.num_steps
+
+    def push(self, after_reset=False, fresh=None):
+        """Record the batch's current outputs as one time step.  fresh (uint8 / bool [N]): for passes that are not steps -
+        batch.reset(mask) (pass the mask) or the destinations of a copy_envs: the named envs start a new history."""
+        b = self.batch
+        f = None
+        if fresh is not None:
+            fresh = self.torch.as_tensor(fresh).to(device=b.device, dtype=self.torch.uint8).reshape(-1).contiguous()
+            if fresh.numel() != self.num_envs:
+                raise ValueError("rollout push: fresh has %d entries for %d envs" % (fresh.numel(), self.num_envs))
+            f = ctypes.c_void_p(fresh.data_ptr())
+        _lib.check(self.L.mwb_rollout_push(b.h, int(bool(after_reset)), f, b._stream()))
+        self._keep = fresh   # alive until the asynchronous kernel has consumed it
+
+    def gather(self, index, dtype=None):
+        """index[i] = t * N + e, t in 0 .. step -> [B, nstack * C, W, H]: the stacked observations VecPyTorchFrameStack held at
+        those steps, bit for bit; float32, or dtype=torch.uint8 (RGB only).  A LongTensor on the batch's device is read in
+        place, without synchronisation: a row whose index is out of range comes back as zeros and is counted (rejected()).
+        Anything that lives on the host is checked first by check_rollout_indices: ValueError, nothing is launched."""
+        torch, b = self.torch, self.batch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.uint8):
+            raise ValueError("rollout gather: dtype must be torch.float32 or torch.uint8")
+        if torch.is_tensor(index) and index.device == b.device:
+            idx = index.reshape(-1).to(torch.int64).contiguous()
+        else:
+            host = index.cpu().numpy() if torch.is_tensor(index) else index
+            idx = torch.from_numpy(check_rollout_indices(host, self.step, self.num_envs)).to(b.device)
+        out = torch.empty((idx.numel(), self.channels, b.W, b.H), dtype=dtype, device=b.device)
+        _lib.check(self.L.mwb_rollout_gather(b.h, ctypes.c_void_p(idx.data_ptr()), int(idx.numel()), ctypes.c_void_p(out.data_ptr()),
+                                             1 if dtype == torch.float32 else 0, b._stream()))
+        self._keep_idx = idx
+        return out
+
+    def obs(self, t, dtype=None):
+        """rollouts.obs[t]: the stacked observations of every env at logical time t (0 .. step)"""
+        t = int(t)
+        if not 0 <= t <= self.step:
+            raise ValueError("rollout obs: t = %d outside 0 .. %d" % (t, self.step))
+        return self.gather(self._arange + t * self.num_envs, dtype=dtype)
+
+    def after_update(self):
+        _lib.check(self.L.mwb_rollout_after_update(self.batch.h, self.batch._stream()))
+
+    def rejected(self):
+        """rows of gathers whose index was out of range since the last call (synchronous)"""
+        out = ctypes.c_ulonglong()
+        _lib.check(self.L.mwb_rollout_rejected(self.batch.h, ctypes.byref(out)))
+        return int(out.value)
+
+
 class _DevView:
     """Exposes a library-owned device buffer through __cuda_array_interface__ (zero-copy)."""
 
@@ -614,6 +724,15 @@ class BatchedMiniWorld:
             _lib.check(self.L.mwb_stack_window(self.h, ctypes.byref(first), None))
             self.stack = self._stack_base[:, first.value:first.value + self._stack_c]
         return self.stack
+
+    # --------------------------------------------------------------------------- rollout storage
+    def rollout_enable(self, num_steps, nstack=4, grey=False):
+        """The observation half of the trainer's RolloutStorage on the device (mwb_rollout_enable): a ring of num_steps + nstack
+        single frames - uint8 RGB, or with grey=True (needs greyscale=True at construction) the float32 grey frames - instead of
+        num_steps + 1 stacked float32 observations, and the rewards / masks / features rows.  Needs layout='CWH'.  Returns the
+        Rollout (also self.rollout): push() after every reset() / step(), gather(idx) for the minibatches."""
+        self.rollout = Rollout(self, num_steps, nstack, grey)
+        return self.rollout
 
     def frame_reuse_stats(self):
         """(frames reused, frames rendered) by the step passes since the last call (mwb_frame_reuse_stats; synchronous).  A step

@@ -10,10 +10,12 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "mwb_internal.h"
 #include "mwb_lds_layout.h"
+#include "mwb_rollout_map.h"
 #include "mwb_task_table.h"
 #include "mwb_texture_host.h"
 
@@ -100,6 +102,10 @@ struct mwb_handle {
     double *rep_sum = nullptr;          // [N] float64 sum of the call's sub-step rewards
     int32_t *rep_taken = nullptr;       // [N] sub-steps taken in the last call (mwb_repeat_taken)
     uint8_t *rep_same = nullptr, *rep_frozen = nullptr;   // [N] each: every sub-step so far left the frame standing / the env takes no further sub-step
+    // ---- the rollout storage (mwb_rollout_enable): its own allocations (not in `allocs`: a failed enable frees what it got)
+    bool rollout_on = false;
+    MwbRollout rollout = {};
+    size_t rollout_ring_bytes = 0;
 };
 #define MWB_COPY_TABLE_DESCS 64
 static unsigned long long g_next_serial = 1;
@@ -352,6 +358,12 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
     return MWB_OK;
 }
 
+static void rollout_free(MwbRollout &r) {
+    void *ps[] = {r.ring, r.age, r.reward, r.mask, r.feature, r.rejected};
+    for (void *p : ps) if (p) hipFree(p);
+    r = MwbRollout{};
+}
+
 extern "C" int mwb_destroy(mwb_handle *h) {
     if (!h) return MWB_OK;
     DevGuard _dev_guard(h->cfg.device);
@@ -360,6 +372,7 @@ extern "C" int mwb_destroy(mwb_handle *h) {
     if (h->texels_dev) hipFree(h->texels_dev);
     if (h->mesh_data_dev) hipFree(h->mesh_data_dev);
     if (h->copy_pairs) hipFree(h->copy_pairs);
+    rollout_free(h->rollout);
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
@@ -872,6 +885,114 @@ extern "C" int mwb_stack_window(mwb_handle *h, int *first_plane, int *planes_per
     return MWB_OK;
 }
 
+// ---------------------------------------------------------------------------------- rollout storage
+// frame ring + per-step rows; the arithmetic is mwb_rollout_map.h, the kernels mwb_rollout.hip
+extern "C" int mwb_rollout_enable(mwb_handle *h, int num_steps, int nstack, unsigned flags) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_enable: null handle");
+    const MwbDev &d = h->dev;
+    if (num_steps < 1 || num_steps > (1 << 24) || nstack < 1 || nstack > 16 || (flags & ~(unsigned)MWB_ROLLOUT_GREY))
+        return set_err(MWB_EINVAL, "mwb_rollout_enable: bad num_steps / nstack / flags");
+    if (d.layout != MWB_LAYOUT_CWH) return set_err(MWB_EINVAL, "mwb_rollout_enable: stacked observations are channel-first, create the handle with MWB_LAYOUT_CWH");
+    if ((d.W * d.H) % 4) return set_err(MWB_EINVAL, "mwb_rollout_enable: W*H must be a multiple of 4");
+    if (h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_enable: already enabled");
+    const int grey = (flags & MWB_ROLLOUT_GREY) != 0;
+    if (grey && !d.grey) return set_err(MWB_ESTATE, "mwb_rollout_enable: MWB_ROLLOUT_GREY needs mwb_grey_enable first");
+    USE_DEVICE(h->cfg.device);
+    MwbRollout r = {};
+    r.N = d.N; r.T = num_steps; r.nstack = nstack; r.R = mwb_rollout_ring_slots(num_steps, nstack); r.grey = grey;
+    r.base = 0; r.cursor = -1;
+    r.frame_bytes = (size_t)d.W * d.H * (grey ? sizeof(float) : 3);
+    const size_t N = (size_t)d.N, T1 = (size_t)num_steps + 1, ring_bytes = (size_t)r.R * N * r.frame_bytes;
+    int rc = MWB_OK;
+    auto get = [&](auto *&p, size_t bytes) {
+        if (rc != MWB_OK) return;
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) { rc = set_err(MWB_ENOMEM, std::string("mwb_rollout_enable: hipMalloc failed: ") + hipGetErrorString(e)); return; }
+        p = static_cast<std::remove_reference_t<decltype(p)>>(q);
+        if ((e = hipMemset(q, 0, bytes)) != hipSuccess) rc = set_err(MWB_EHIP, std::string("mwb_rollout_enable: hipMemset failed: ") + hipGetErrorString(e));
+    };
+    get(r.ring, ring_bytes); get(r.age, T1 * N); get(r.reward, (size_t)num_steps * N * sizeof(float)); get(r.mask, T1 * N * sizeof(float));
+    get(r.feature, T1 * N * 2 * sizeof(float)); get(r.rejected, sizeof(unsigned long long));
+    if (rc == MWB_OK && hipDeviceSynchronize() != hipSuccess) rc = set_err(MWB_EHIP, "mwb_rollout_enable: hipDeviceSynchronize failed");
+    if (rc != MWB_OK) { rollout_free(r); return rc; }   // the handle is as it was
+    h->rollout = r; h->rollout_ring_bytes = ring_bytes; h->rollout_on = true;
+    return MWB_OK;
+}
+
+extern "C" int mwb_rollout_push(mwb_handle *h, int after_reset, const uint8_t *fresh_dev, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_push: null handle");
+    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_push: call mwb_rollout_enable first");
+    MwbRollout &r = h->rollout;
+    if (!after_reset && r.cursor < 0) return set_err(MWB_ESTATE, "mwb_rollout_push: the first push must follow a reset (after_reset != 0)");
+    if (!after_reset && r.cursor >= r.T) return set_err(MWB_ESTATE, "mwb_rollout_push: the rollout holds num_steps steps already: call mwb_rollout_after_update");
+    USE_DEVICE(h->cfg.device);
+    const MwbDev &d = h->dev;
+    hipStream_t s = (hipStream_t)stream;
+    const int t = after_reset ? 0 : r.cursor + 1;
+    // the frames of a slot are one contiguous slab in the order of the output buffer: a device-to-device copy, no kernel
+    const size_t slab = (size_t)r.N * r.frame_bytes;
+    const void *frames = r.grey ? (const void *)d.grey : (const void *)d.obs;
+    HIP_TRY(hipMemcpyAsync(r.ring + (size_t)mwb_rollout_slot(r.base, t, 0, r.R) * slab, frames, slab, hipMemcpyDeviceToDevice, s));
+    mwb_launch_rollout_push(r, t, after_reset != 0, fresh_dev, d.done, d.reward, d.feature, s);
+    if (int rc = check_launch("rollout_push_kernel")) return rc;
+    r.cursor = t;
+    return MWB_OK;
+}
+
+extern "C" int mwb_rollout_gather(mwb_handle *h, const int64_t *index_dev, int count, void *out_dev, int dtype, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_gather: null handle");
+    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_gather: call mwb_rollout_enable first");
+    const MwbRollout &r = h->rollout;
+    if (dtype != 0 && dtype != 1) return set_err(MWB_EINVAL, "mwb_rollout_gather: dtype must be 0 (uint8) or 1 (float32)");
+    if (r.grey && dtype == 0) return set_err(MWB_EINVAL, "mwb_rollout_gather: a grey rollout is gathered as float32 (the reference defines no uint8 grey)");
+    if (count < 0) return set_err(MWB_EINVAL, "mwb_rollout_gather: count < 0");
+    if (r.cursor < 0) return set_err(MWB_ESTATE, "mwb_rollout_gather: nothing has been pushed yet");
+    if (count == 0) return MWB_OK;
+    if (!index_dev || !out_dev) return set_err(MWB_EINVAL, "mwb_rollout_gather: null argument");
+    if ((uintptr_t)out_dev & 15) return set_err(MWB_EINVAL, "mwb_rollout_gather: out_dev must be 16-byte aligned");
+    USE_DEVICE(h->cfg.device);
+    mwb_launch_rollout_gather(r, index_dev, count, out_dev, dtype, (hipStream_t)stream);
+    return check_launch("rollout_gather_kernel");
+}
+
+extern "C" int mwb_rollout_after_update(mwb_handle *h, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_after_update: null handle");
+    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_after_update: call mwb_rollout_enable first");
+    MwbRollout &r = h->rollout;
+    if (r.cursor < 0) return set_err(MWB_ESTATE, "mwb_rollout_after_update: nothing has been pushed yet");
+    USE_DEVICE(h->cfg.device);
+    mwb_launch_rollout_after_update(r, (hipStream_t)stream);
+    if (int rc = check_launch("rollout_after_update_kernel")) return rc;
+    r.base = mwb_rollout_next_base(r.base, r.T, r.R);
+    r.cursor = 0;
+    return MWB_OK;
+}
+
+extern "C" int mwb_rollout_info(mwb_handle *h, struct mwb_rollout_info *out) {
+    if (!h || !out) return set_err(MWB_EINVAL, "mwb_rollout_info: null argument");
+    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_info: call mwb_rollout_enable first");
+    const MwbRollout &r = h->rollout;
+    const size_t N = (size_t)r.N, T1 = (size_t)r.T + 1;
+    memset(out, 0, sizeof(*out));
+    out->reward = r.reward; out->mask = r.mask; out->feature = r.feature; out->age = r.age; out->ring = r.ring;
+    out->reward_bytes = (size_t)r.T * N * sizeof(float); out->mask_bytes = T1 * N * sizeof(float);
+    out->feature_bytes = T1 * N * 2 * sizeof(float); out->age_bytes = T1 * N; out->ring_bytes = h->rollout_ring_bytes;
+    out->num_steps = r.T; out->nstack = r.nstack; out->grey = r.grey; out->cursor = r.cursor; out->base = r.base;
+    return MWB_OK;
+}
+
+extern "C" int mwb_rollout_rejected(mwb_handle *h, unsigned long long *rows) {
+    if (!h || !rows) return set_err(MWB_EINVAL, "mwb_rollout_rejected: null argument");
+    *rows = 0;
+    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_rejected: call mwb_rollout_enable first");
+    USE_DEVICE(h->cfg.device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(rows, h->rollout.rejected, sizeof(*rows), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(h->rollout.rejected, 0, sizeof(*rows)));
+    HIP_TRY(hipDeviceSynchronize());
+    return MWB_OK;
+}
 
 // ------------------------------------------------------------------------------ copying environments
 // the first field of the two configurations that differs (num_envs and domain_rand may), or null.  Compared as the handles use

@@ -337,6 +337,25 @@ void mwb_launch_copy_stack(char *dst, size_t env_bytes_dst, size_t off_dst, cons
 void mwb_launch_repeat_fold(const MwbDev &d, int sub, int last, int repeat, const uint8_t *skip, const int32_t *counts, double *sum,
                             int32_t *taken, uint8_t *same, uint8_t *frozen, hipStream_t s);
 
+// ---- the rollout storage (mwb_rollout_enable; mwb_rollout_map.h says where a frame lives).  Passed by value to the kernels of
+// mwb_rollout.hip; base and cursor are the host's (a captured graph of these launches must not be replayed).
+struct MwbRollout {
+    int N, T, nstack, R;    // envs, num_steps, frames per stacked observation, ring slots = T + nstack
+    int grey;               // the ring holds the float32 grey frames (1 plane) instead of the uint8 RGB ones (3 planes)
+    int base, cursor;       // slot of logical time 0; the last time pushed (-1: none since mwb_rollout_enable)
+    size_t frame_bytes;     // one env's frame in a slot: W*H*3, or W*H*4 for grey
+    char *ring;             // [R][N][frame_bytes]
+    uint8_t *age;           // [T + 1][N]
+    float *reward, *mask, *feature;   // [T][N], [T + 1][N], [T + 1][N][2]
+    unsigned long long *rejected;     // [1] rows of gathers whose index was out of range since mwb_rollout_rejected last read it
+};
+// launch wrappers implemented in mwb_rollout.hip.  push: time t (> 0, or 0 with after_reset) from the handle's done / reward /
+// feature outputs; gather: count > 0 rows, out 16-byte aligned, out_float = 1 for a grey ring
+void mwb_launch_rollout_push(const MwbRollout &r, int t, int after_reset, const uint8_t *fresh_dev, const uint8_t *done, const float *reward,
+                             const float *feature, hipStream_t s);
+void mwb_launch_rollout_after_update(const MwbRollout &r, hipStream_t s);
+void mwb_launch_rollout_gather(const MwbRollout &r, const int64_t *index, int count, void *out, int out_float, hipStream_t s);
+
 // launch wrappers implemented in mwb_kernels.hip
 void mwb_launch_step(const MwbDev &d, const int32_t *actions, const uint8_t *skip_mask, hipStream_t s);   // entity tasks: step_ents_kernel
 void mwb_launch_clear_list(const MwbDev &d, hipStream_t s);

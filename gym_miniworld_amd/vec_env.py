@@ -129,6 +129,11 @@ class MiniWorldVecEnv(VecEnv):
     frame_skip=k    -> action repeat: a step() is up to k sub-steps of the env with the one action, stopped by done, of which only
                        the last frame is rendered (mwb_step_repeat); the reward is the sum, info['taken'] the number of
                        sub-steps (infos.taken for the whole batch).  The frame stack holds one frame per step().
+    rollout_steps=T -> the trainer's RolloutStorage kept on the device (BatchedMiniWorld.rollout_enable): `envs.rollout` holds every
+                       frame of the last T steps once, pushed by reset() and by every step, with nstack = frame_stack (1 without)
+                       and the grey frames with greyscale=True; envs.rollout.gather(idx) rebuilds the stacked observations of a
+                       minibatch, envs.rollout.after_update() replaces rollouts.after_update().  A step beyond T raises the
+                       library's MWB_ESTATE message before anything is stepped.  Not with graph=True (host-side cursor)
     feature_info    -> every info dict carries "feature" (length-2 zeros) as the fork's PPO loop
                        requires (pytorch-a2c-ppo-acktr/main.py:614-619)
     graph=True      -> after two eager steps the whole step (mwb_step's kernels on both streams, the frame-stack /
@@ -143,12 +148,17 @@ class MiniWorldVecEnv(VecEnv):
 
     def __init__(self, env_id, num_envs, seed=1, device=0, domain_rand=False, transpose=True, to_float=True,
                  frame_stack=0, torch_api=True, feature_info=False, first_env_index=0, graph=False, greyscale=False, frame_skip=1,
-                 **kwargs):
+                 rollout_steps=0, **kwargs):
         import torch
         from .batch import BatchedMiniWorld
         from . import _lib
         self.torch = torch
         self.greyscale = bool(greyscale)
+        if rollout_steps and graph:
+            raise ValueError("rollout_steps cannot be combined with graph=True: the rollout's cursor and ring position live on the "
+                             "host, a replayed graph would freeze them")
+        if rollout_steps and not transpose:
+            raise ValueError("rollout_steps needs transpose=True: the rollout stores channel-first frames")
         from .batch import check_repeat_args
         self.frame_skip = check_repeat_args(frame_skip, num_envs, num_envs, name="frame_skip")
         assert to_float or not self.greyscale, "greyscale observations are float32 (GreyscaleWrapper + .float()): to_float=True"
@@ -173,6 +183,8 @@ class MiniWorldVecEnv(VecEnv):
                     raise
                 # observations rendered in tiles (frames too large for one workgroup's LDS, MWB_TILE): the sliding window, one pass
                 self.stackedobs = b.stack_enable(self.nstack, "float32" if to_float else "uint8", sliding=not graph, fused=False)
+        # the trainer's RolloutStorage on the device: pushed by reset() and by the device part of every step
+        self.rollout = b.rollout_enable(int(rollout_steps), nstack=self.nstack or 1, grey=self.greyscale) if rollout_steps else None
         VecEnv.__init__(self, num_envs, Box(0, 255, shape, np.float32 if to_float else np.uint8), Discrete(b.n_actions))
         self.device = b.device
         self.feature_info = feature_info
@@ -215,18 +227,25 @@ class MiniWorldVecEnv(VecEnv):
     # ----------------------------------------------------------------------------------- VecEnv
     def reset(self):
         self.batch.reset()
+        if self.rollout is not None:
+            self.rollout.push(after_reset=True)
         return self._obs_out()
 
     def _device_step(self, a, skip):
         """everything of a step that runs on the device: the stepper + renderer, the learner-side layout pass and the
         asynchronous copies of the small outputs into the pinned host mirrors"""
         b = self.batch
+        ro = self.rollout
+        if ro is not None and ro.full:
+            ro.push()   # raises the library's MWB_ESTATE (call after_update) BEFORE the envs are stepped: nothing changes
         if self.frame_skip > 1:
             b.step_repeat(a, self.frame_skip, skip_mask=skip)
         elif skip is None and a.dtype == self.torch.int64:
             b.step_longtensor(a)
         else:
             b.step(a, skip_mask=skip)
+        if ro is not None:
+            ro.push()
         obs = self._obs_out(done=b.done)
         self._h_pack.copy_(b.pack[:self._pack_need], non_blocking=True)   # one copy: the small outputs share an allocation
         if self._h_taken is not None:

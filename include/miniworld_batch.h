@@ -377,13 +377,78 @@ int mwb_grey_convert(mwb_handle *h, const uint8_t *rgb_dev, float *grey_dev, int
  * PRECONDITION: the source's stack is current - for the non-fused forms mwb_stack_update has been called after the source's last
  * pass.  (3) The destination's stack is fused and the source has none or another one: the destination env gets what a
  * regenerated env gets, a zeroed history and its frame in the newest planes; MWB_EINVAL under MWB_COPY_NO_RENDER.  (4) The
- * destination's stack is not fused and the source has none or another one: MWB_EINVAL. */
+ * destination's stack is not fused and the source has none or another one: MWB_EINVAL.
+ *
+ * Rollout storage (mwb_rollout_enable, below).  A copy touches no rollout, of either handle: the caller restarts the destinations'
+ * history by naming them in the `fresh_dev` of its next mwb_rollout_push. */
 #define MWB_COPY_NO_RENDER 1
 int mwb_copy_envs(mwb_handle *dst, const int32_t *dst_idx_dev, mwb_handle *src, const int32_t *src_idx_dev,
                   int count, unsigned flags, void *stream);
 int mwb_copy_rejected(mwb_handle *dst, unsigned long long *pairs);   /* synchronous; reads and clears */
 /* bytes of per-env state one accepted pair of a copy from src into dst moves (for measurements); negative code on mismatch */
 long long mwb_copy_env_bytes(mwb_handle *dst, mwb_handle *src);
+
+/* ---- rollout storage on the device: frame ring and stacked-minibatch gather ------------------------ */
+/* replaces: the observation half of RolloutStorage (pytorch-a2c-ppo-acktr/storage.py:12,55,75,121) together with its masks,
+ * rewards and features rows - a [num_steps + 1][N] array of STACKED float32 observations, written with
+ * obs[step + 1].copy_(obs) and read with obs[:-1].view(-1, ...)[indices].  The rollout keeps every single frame once, in the
+ * format the handle renders it (uint8 RGB, or the float32 grey frame), in a time-major ring of R = num_steps + nstack slots
+ * [R][N][C][W][H] (C = 3, or 1 for grey), plus one byte of "age" per (step, env): how many earlier frames belong to the stacked
+ * observation VecPyTorchFrameStack (envs.py:135-165) held there.  mwb_rollout_gather rebuilds any stacked row from them, bit for
+ * bit.  Logical time t lives in slot (base + t) mod R, the frame j steps before it in slot (base + t - j + R) mod R - for
+ * t - j < 0 these are the last frames of the window before (csrc/mwb_rollout_map.h has the arithmetic and why R is the smallest
+ * ring that works).  base and the cursor live on the host, as the sliding frame stack's window position does: a captured graph
+ * of these calls must not be replayed.
+ *
+ * mwb_rollout_enable (replaces RolloutStorage.__init__, storage.py:10-25): num_steps >= 1, nstack in 1 .. 16, flags 0 or
+ * MWB_ROLLOUT_GREY (the ring of the grey frames).  MWB_EINVAL: the handle is not MWB_LAYOUT_CWH, or W*H is no multiple of 4 (the
+ * frame stack's own rules), or a bad argument.  MWB_ESTATE: already enabled, or MWB_ROLLOUT_GREY without mwb_grey_enable.  May be
+ * called at any time: it reads only the output buffers (handles whose frames are rendered in tiles included).  Allocates the ring,
+ * age u8 [T + 1][N], reward f32 [T][N], mask f32 [T + 1][N], feature f32 [T + 1][N][2] (T = num_steps); mwb_destroy frees them.
+ * mwb_copy_envs does not touch a rollout: the caller restarts the destinations' history with `fresh_dev`, below. */
+#define MWB_ROLLOUT_GREY 1
+int mwb_rollout_enable(mwb_handle *h, int num_steps, int nstack, unsigned flags);
+/* replaces: rollouts.obs[0].copy_(obs) after envs.reset() (after_reset != 0) and RolloutStorage.insert (storage.py:52-66,
+ * after_reset == 0): records the handle's current outputs as one logical time step, enqueued on `stream` after the pass that
+ * produced them.
+ * after_reset != 0: the cursor becomes 0, frame(0) = obs (or grey), age[0] = 0, mask[0] = 1, feature[0] = 0 for every env
+ *   (VecPyTorchFrameStack.reset, envs.py:158-162; the initial masks / features of RolloutStorage).
+ * after_reset == 0: the cursor becomes t = cursor + 1, frame(t) = obs; with fresh[e] = fresh_dev ? fresh_dev[e] != 0 : done[e]:
+ *   age[t][e] = fresh ? 0 : min(age[t-1][e] + 1, nstack - 1), mask[t][e] = fresh ? 0 : 1, feature[t][e] = feature[e] (the
+ *   features[step + 1] convention, storage.py:67), reward[t-1][e] = reward[e], or 0 when fresh_dev is given.
+ * fresh_dev (device u8[num_envs] or NULL) is for passes that are not steps - a partial mwb_reset(mask), where the caller passes
+ * its mask, or the destinations of an mwb_copy_envs: the named envs start a new history, the others get their current frame
+ * appended once more (the rule stated above for the fused stack's partial reset).  A skipped env (reward -99, done 0) is simply an
+ * env that is not done; mwb_step_repeat is one frame per call.
+ * MWB_ESTATE, and nothing changes: no after_reset push has been made yet, or the cursor is already num_steps (call
+ * mwb_rollout_after_update). */
+int mwb_rollout_push(mwb_handle *h, int after_reset, const uint8_t *fresh_dev, void *stream);
+/* replaces: obs.view(-1, *obs.size()[2:])[indices] of the minibatch generators (storage.py:121) and obs[step] of the acting loop.
+ * index_dev: device i64[count], index_dev[i] = t * N + e with t in 0 .. cursor - the flat index of that view, t = num_steps (the
+ * bootstrap observation) allowed; any order, repeats allowed; read on the device, no synchronisation.  Row i of out_dev (device
+ * memory, 16-byte aligned) is [nstack * C][W][H], contiguous: float32 for dtype 1 (uint8 -> float32 is exact, grey frames are
+ * copied bitwise), uint8 for dtype 0 (MWB_EINVAL for a grey ring: the reference defines no uint8 grey).  Frame group k (0 =
+ * oldest) is frame t - j with j = nstack - 1 - k if j <= age[t][e], zeros otherwise.  A row whose index is negative or
+ * >= (cursor + 1) * N is written as zeros and counted (mwb_rollout_rejected); nothing is read or written outside the ring and
+ * the `count` rows.  count == 0 is a no-op.  MWB_ESTATE before the first push. */
+int mwb_rollout_gather(mwb_handle *h, const int64_t *index_dev, int count, void *out_dev, int dtype, void *stream);
+/* replaces: RolloutStorage.after_update (storage.py:69-73): row num_steps of age, mask and feature becomes row 0, base moves
+ * num_steps slots on and the cursor becomes 0 - no frame moves.  MWB_ESTATE before the first push. */
+int mwb_rollout_after_update(mwb_handle *h, void *stream);
+/* the rollout's device arrays (fixed for the handle's lifetime) and its position.  The struct has a tag only, no typedef: the
+ * function below bears the same name, so the type is always written `struct mwb_rollout_info` */
+struct mwb_rollout_info {
+    float *reward, *mask, *feature;   /* f32 [T][N], [T+1][N], [T+1][N][2] */
+    uint8_t *age;                     /* u8 [T+1][N] */
+    void *ring;                       /* [R][N][C][W][H], u8 or (grey) f32 */
+    size_t reward_bytes, mask_bytes, feature_bytes, age_bytes, ring_bytes;
+    int32_t num_steps, nstack, grey;
+    int32_t cursor;                   /* the last logical time pushed; -1 before the first after_reset push */
+    int32_t base;                     /* ring slot of logical time 0 */
+    int32_t pad;
+};
+int mwb_rollout_info(mwb_handle *h, struct mwb_rollout_info *out);   /* MWB_ESTATE before mwb_rollout_enable */
+int mwb_rollout_rejected(mwb_handle *h, unsigned long long *rows);   /* synchronous; reads and clears */
 
 /* World generation cannot fail for the four tasks with sane arguments; if it ever does (a portal outside
  * its wall, more than one portal on an edge, a placement that finds no free spot in 100000 draws - the
