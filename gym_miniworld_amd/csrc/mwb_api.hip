@@ -271,6 +271,7 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
     // the environment's knobs
     { const char *dbg = getenv("MWB_DEBUG"); d.debug_flags = dbg ? atoi(dbg) : 0; }
     { const char *ex = getenv("MWB_EXP"); d.exp_flags = ex ? atoi(ex) : 0; }
+    { const char *no = getenv("MWB_NO_SEG_CULL"); d.no_seg_cull = no && atoi(no); }
     { const char *no = getenv("MWB_NO_OVERLAP"); h->overlap_reset = !(no && atoi(no)); }
     {   // the last ~0.6 round of resident workgroups (5 per CU x 256 CUs = 1280) of a bulk render launch drains in
         // half-frame units: measured best between 640 and 960 envs (+4 % at 8192 Maze envs); MWB_SPLIT overrides
@@ -1086,6 +1087,8 @@ extern "C" int mwb_copy_envs(mwb_handle *dst, const int32_t *dst_idx_dev, mwb_ha
     rc = check_launch("copy_validate_kernel"); if (rc) return rc;
     mwb_launch_copy_envs(dst->copy_tables + (size_t)slot * MWB_COPY_TABLE_DESCS, tab.n_small, tab.small_chunks, tab.n_large, dst->copy_pairs, count, s);
     rc = check_launch("copy_envs_kernel"); if (rc) return rc;
+    mwb_launch_copy_seg_box(d, dst->copy_pairs, count, s);
+    rc = check_launch("copy_seg_box_kernel"); if (rc) return rc;
     dst->have_world = true;
     if (render) {   // the destinations through the compact-list path, as mwb_render draws them: the current state, every frame rendered
         d.step_pass = 0; d.reuse_pass = 0;

@@ -12,10 +12,13 @@
 //                         is 2500 bytes: only 4-byte aligned).  Whole rows, not their live part.
 //   copy_list_kernel      the accepted destinations onto / off the handle's reset_set + reset_list (the existing mode-1
 //                         prep and render launches then draw exactly these), or their frame_cached flags down.
+//   copy_seg_box_kernel   the group boxes of the copied collision segments (d.seg_box, mwb_seg_groups.h), rebuilt from the
+//                         destination's segments - derived data, not on the list of copied arrays.
 //   copy_stack_kernel     the visible window of the frame stack, a workgroup per pair and 32 KB of it.
 // No scratch, no LDS; a pair that is not carried out costs its lane one 8-byte load.
 #include "mwb_internal.h"
 #include "mwb_copy_check.h"
+#include "mwb_seg_groups.h"
 
 #define COPY_THREADS 256
 
@@ -100,6 +103,28 @@ __global__ void __launch_bounds__(COPY_THREADS) copy_list_kernel(MwbDev d, const
     }
 }
 
+// one lane per (pair, segment group): after copy_envs_kernel the destination's n_segs and segs are its source's
+__global__ void __launch_bounds__(COPY_THREADS) copy_seg_box_kernel(MwbDev d, const int2 *__restrict__ pairs, int count) {
+    const size_t G = (size_t)mwb_seg_groups(d.S_max), N = (size_t)d.N;
+    for (size_t i = (size_t)blockIdx.x * COPY_THREADS + threadIdx.x; i < (size_t)count * G; i += (size_t)gridDim.x * COPY_THREADS) {
+        const int dst = pairs[i / G].x, g = (int)(i % G);
+        if (dst < 0) continue;
+        const int ns = d.n_segs[dst] < d.S_max ? d.n_segs[dst] : d.S_max, n = ns - g * MWB_SEG_GROUP < MWB_SEG_GROUP ? ns - g * MWB_SEG_GROUP : MWB_SEG_GROUP;
+        if (n < 1) continue;   // no reader looks at a group past the env's segments
+        double q[MWB_SEG_GROUP * 4];
+#pragma unroll
+        for (int k = 0; k < MWB_SEG_GROUP * 4; k++) q[k] = d.segs[((size_t)g * MWB_SEG_GROUP * 4 + (k < n * 4 ? k : 0)) * N + dst];
+        const MwbSegBox b = mwb_seg_group_box(q, n);
+        float *o = d.seg_box + (size_t)g * 4 * N + dst;
+        o[0] = b.min_x; o[N] = b.min_z; o[2 * N] = b.max_x; o[3 * N] = b.max_z;
+        if (d.seg_rows) {   // and the env-major twin of the group
+            double *r = d.seg_rows + ((size_t)dst * d.S_max + (size_t)g * MWB_SEG_GROUP) * 4;
+#pragma unroll
+            for (int k = 0; k < MWB_SEG_GROUP * 4; k++) if (k < n * 4) r[k] = q[k];
+        }
+    }
+}
+
 #define COPY_STACK_RUN 32768   // bytes of one env's window a workgroup moves
 __global__ void __launch_bounds__(COPY_THREADS) copy_stack_kernel(char *dst, size_t env_bytes_dst, size_t off_dst, const char *src,
                                                                   size_t env_bytes_src, size_t off_src, size_t window_bytes, const int2 *__restrict__ pairs) {
@@ -131,6 +156,11 @@ void mwb_launch_copy_envs(const MwbCopyDesc *table, int n_small, int small_chunk
 
 void mwb_launch_copy_list(const MwbDev &d, const int2 *pairs, int count, int what, hipStream_t s) {
     hipLaunchKernelGGL(copy_list_kernel, dim3(pair_blocks(count)), dim3(COPY_THREADS), 0, s, d, pairs, count, what);
+}
+
+void mwb_launch_copy_seg_box(const MwbDev &d, const int2 *pairs, int count, hipStream_t s) {
+    const long long b = ((long long)count * mwb_seg_groups(d.S_max) + COPY_THREADS - 1) / COPY_THREADS;
+    hipLaunchKernelGGL(copy_seg_box_kernel, dim3((unsigned)(b < 1 ? 1 : b > 4096 ? 4096 : b)), dim3(COPY_THREADS), 0, s, d, pairs, count);
 }
 
 void mwb_launch_copy_stack(char *dst, size_t env_bytes_dst, size_t off_dst, const char *src, size_t env_bytes_src, size_t off_src,

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "../../include/miniworld_batch.h"
+#include "mwb_seg_groups.h"
 
 #define MWB_MT_WORDS 625   // 624 key words + pos
 #define MWB_MAX_TEX MWB_NUM_TEXTURES
@@ -233,7 +234,16 @@ struct MwbDev {
     // ---- mwb_step_repeat (last on purpose: no other member's offset moves).  Null except in the launches of sub-steps 2..k of
     // such a call, where the step kernels leave env e untouched when frozen[e] is set (mwb_repeat_fold.h, repeat_fold_kernel)
     const uint8_t *frozen;  // [N]
+    // ---- bounding boxes of the collision segments in groups of MWB_SEG_GROUP (mwb_seg_groups.h), written by reset_kernel beside
+    // d.segs and read ahead of them by every circle-vs-walls loop: a group whose box excludes the point is not loaded
+    float *seg_box;         // [ceil(S_max / MWB_SEG_GROUP)][4][N] min_x min_z max_x max_z, float32 rounded outwards; transposed like segs
+    int no_seg_cull;        // MWB_NO_SEG_CULL=1 at mwb_create: every group passes (A/B and the tests of the cull itself)
+    // worlds step_kernel culls (mwb_step_culls): the segments once more, env-major, so that the few groups an env does load are
+    // 256 contiguous bytes each - out of the transposed block a single lane's group is 32 lines, 4 KB of traffic.  Null otherwise
+    double *seg_rows;       // [N][S_max][4]
 };
+// step_kernel culls by group where a wave (it has STEP_PARTS = 8) would otherwise walk a chain of batches: more than 64 segments
+MWB_SEG_HD static inline bool mwb_step_culls(int S_max) { return mwb_seg_groups(S_max) > 8; }
 
 // ---- the per-env device arrays of MwbDev, each written down ONCE: mwb_create allocates from this list, mwb_copy_envs builds its
 // descriptor table from it and mwb_copy_env_bytes sums it.  A new array is one new line here (and its member above), no second
@@ -279,6 +289,8 @@ static inline void mwb_for_each_env_array(Dev &s, Dev &d, bool frame_reuse, F &&
     MWB_MAJOR(rng, MWB_MT_WORDS, always, COPIED);
     MWB_MAJOR(rooms, (size_t)s.R_max * s.room_words, always, COPIED);
     MWB_MINOR(segs, s.S_max * 4, 1, always, COPIED);
+    MWB_MINOR(seg_box, mwb_seg_groups(s.S_max) * 4, 1, always, "derived from segs: copy_seg_box_kernel rebuilds it from the copied segments");
+    MWB_MAJOR(seg_rows, (size_t)s.S_max * 4, mwb_step_culls(s.S_max), "derived from segs: copy_seg_box_kernel rebuilds it from the copied segments");
     MWB_MINOR(ent_meta, B, 1, ent, COPIED); MWB_MINOR(ent_radius, B, 1, ent, COPIED); MWB_MINOR(ent_height, B, 1, ent, COPIED);
     MWB_MINOR(ent_scale, B, 1, ent, COPIED);
     MWB_MAJOR(ent_order, MWB_ORDER_STRIDE, ent, COPIED); MWB_MINOR(n_order, 1, 1, ent, COPIED);
@@ -329,6 +341,8 @@ void mwb_launch_copy_envs(const MwbCopyDesc *table, int n_small, int small_chunk
 // what: 0 = put the destinations on d's reset_set / reset_list (before the list render), 1 = take them off again and empty the
 // list (after it), 2 = no render: their cached frames no longer show their state
 void mwb_launch_copy_list(const MwbDev &d, const int2 *pairs, int count, int what, hipStream_t s);
+// the destinations' segment group boxes (d.seg_box) from the segments mwb_launch_copy_envs has just copied
+void mwb_launch_copy_seg_box(const MwbDev &d, const int2 *pairs, int count, hipStream_t s);
 // the visible window of the frame stack: env_bytes_* = bytes between consecutive envs, off_* = byte offset of the window's first plane
 void mwb_launch_copy_stack(char *dst, size_t env_bytes_dst, size_t off_dst, const char *src, size_t env_bytes_src, size_t off_src,
                            size_t window_bytes, const int2 *pairs, int count, hipStream_t s);

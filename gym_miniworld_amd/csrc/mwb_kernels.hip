@@ -121,6 +121,26 @@ __device__ __forceinline__ bool seg_hit(SegPtr sg, double px, double pz, double 
     return dist < radius;
 }
 
+// circle vs ALL of env e's wall segments by one lane (the carry / pickup tests, the entity tasks, mwb_intersect): group by group,
+// the group's box first (d.seg_box, mwb_seg_groups.h).  A group whose box grown by radius + 1e-9 excludes the point has no segment
+// within the radius - seg_hit would say no to each - so its segments are not loaded.
+__device__ __forceinline__ bool walls_hit_serial(const MwbDev &d, int e, int ns, double px, double pz, double radius) {
+    const size_t N = (size_t)d.N;
+    const double guard = radius + 1e-9;
+    for (int g = 0; g * MWB_SEG_GROUP < ns; g++) {
+        const float *b = d.seg_box + (size_t)g * 4 * N + e;
+        if (!d.no_seg_cull && !mwb_seg_box_near(b[0], b[N], b[2 * N], b[3 * N], px, pz, guard)) continue;
+        const int i1 = (g + 1) * MWB_SEG_GROUP < ns ? (g + 1) * MWB_SEG_GROUP : ns;
+        for (int i = g * MWB_SEG_GROUP; i < i1; i++) {
+            double q[4];
+#pragma unroll
+            for (int c = 0; c < 4; c++) q[c] = d.segs[(size_t)(i * 4 + c) * N + e];
+            if (seg_hit(q, px, pz, radius)) return true;
+        }
+    }
+    return false;
+}
+
 
 // a + b as the reference's interpreter evaluates it when either may be a numpy float32 SCALAR (a MeshEnt's radius under
 // NumPy >= 2, entity.py:118-127) and the other a Python float: the Python float is cast to float32, the sum is a float32
@@ -139,7 +159,10 @@ __device__ __forceinline__ double box_radius(double size) {
 // Wave 0 carries the sequential part of MiniWorldEnv.step; the circle-vs-segments test of a forward move -
 // the only loop, up to 256 segments in Maze - is split over all waves (wave p takes the 8-segment batches
 // p, p + STEP_PARTS, ...), which turns one long dependent load chain per env into STEP_PARTS short ones.
+// Each batch has a float32 bounding box (d.seg_box): a wave loads the boxes of its batches, STEP_BOXES of them at a time, and
+// only the batches whose box the point is near - of Maze's 32 usually one to three - are loaded at all, dealt out over the waves.
 #define STEP_PARTS 8
+#define STEP_BOXES 4
 // NBX = the task's number of boxes (1, 2 or 6): a template parameter so that the one-box tasks do not carry six-wide
 // select chains through the sequential part
 template <int NBX>
@@ -147,6 +170,7 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
                                                                 const uint8_t *__restrict__ skip) {
     __shared__ double s_nx[64], s_nz[64];
     __shared__ int s_move[64], s_hit[64];
+    __shared__ uint8_t s_near[STEP_PARTS][64];
     const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
     const int e = blockIdx.x * 64 + lane;
     const bool in_range = e < d.N;
@@ -166,6 +190,21 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
     const double arad = d.agent_radius;
     if (blockIdx.x == 0 && threadIdx.x == 0 && d.order_state[1]) {   // adopt the dispatch order completed beside the last pass
         d.order_state[0] ^= 1; d.order_state[1] = 0;                  // (nothing reads the maps while step_kernel runs)
+    }
+    // The boxes of this wave's segment groups (d.seg_box, see below) do not depend on where the agent goes: their loads are issued
+    // here, ahead of wave 0's sequential part, and are back when the move is known.  Block-uniform: a world of up to 64 segments
+    // gives every wave one batch at the most - there is no chain of batches to cut short, the batch is loaded at once as it was
+    // before there were boxes (a box test first measured 3 us slower on FourRooms x 16384) - so the cull is for larger worlds.
+    const size_t segN = (size_t)d.N;
+    const int NG = mwb_seg_groups(d.S_max);
+    static_assert(STEP_PARTS == 8, "mwb_step_culls (mwb_internal.h) states the same threshold");
+    const bool cull = mwb_step_culls(d.S_max);   // (d.seg_rows exists)
+    float bb[STEP_BOXES][4];
+#pragma unroll
+    for (int j = 0; j < STEP_BOXES; j++) {
+        const int g = part + j * STEP_PARTS < NG ? part + j * STEP_PARTS : 0;   // clamp: an allocated box, its verdict is dropped below
+#pragma unroll
+        for (int c = 0; c < 4; c++) bb[j][c] = cull && in_range ? d.seg_box[(size_t)(g * 4 + c) * segN + e] : 0.0f;
     }
     if (part == 0) {
         s_move[lane] = 0; s_hit[lane] = 0;
@@ -251,24 +290,33 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
         }
     }
     __syncthreads();
-    if (live && s_move[lane]) {
+    {
         // segments are stored transposed (segment-major, env-minor) so that the lanes of a wave - one
         // env each - read consecutive addresses.  No early exit (keeps the loads independent); a
         // segment whose bounding box grown by the radius (+1e-9 guard) excludes the point cannot be
         // within the radius, so skipping it is exact.
+        // The groups' float32 boxes decide first (16 bytes a group against 256): a group whose box, grown by the same guard, excludes
+        // the point holds no segment the per-segment reject below would let through, so it is not loaded.  Wave p tests the boxes
+        // of groups p, p + 8, .. (loaded above) and leaves its verdicts in s_near; the few groups of an env that pass - of Maze's
+        // 32 usually one to three - are then dealt out over the waves again, the k-th of them to wave k mod 8, so that they are
+        // loaded side by side: one round of box loads and one of segment loads instead of a chain of four.
+        const bool mover = live && s_move[lane];
         const double px = s_nx[lane], pz = s_nz[lane];
         const double *sg = d.segs + e;
-        const size_t N = (size_t)d.N;
-        const int ns = d.n_segs[e];
+        const int ns = mover ? d.n_segs[e] : 0, ng = mwb_seg_groups(ns);
         bool hit = false;
         const double guard = arad + 1e-9;
-        for (int i0 = part * 8; i0 < ns; i0 += 8 * STEP_PARTS) {   // 8 segments (32 coalesced loads) in flight, then the tests
+        // a culled world loads the few batches that pass from the env-major twin of the segments (d.seg_rows): 256 contiguous bytes
+        // a batch, where the transposed block costs a lone lane 32 lines
+        const double *qb = cull ? d.seg_rows + (size_t)e * d.S_max * 4 : sg;
+        const size_t qs = cull ? 1 : segN;
+        auto test_batch = [&](int i0) {   // 8 segments (32 loads) in flight, then the tests
             double q[8][4];
 #pragma unroll
             for (int k = 0; k < 8; k++) {
                 const int i = (i0 + k < ns) ? i0 + k : ns - 1;   // clamp: re-testing a segment is harmless
 #pragma unroll
-                for (int c = 0; c < 4; c++) q[k][c] = sg[(size_t)(i * 4 + c) * N];
+                for (int c = 0; c < 4; c++) q[k][c] = qb[(size_t)(i * 4 + c) * qs];
             }
 #pragma unroll
             for (int k = 0; k < 8; k++) {
@@ -276,6 +324,37 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
                               pz >= fmin(q[k][1], q[k][3]) - guard && pz <= fmax(q[k][1], q[k][3]) + guard;
                 if (nearby) hit = seg_hit(q[k], px, pz, arad) || hit;
             }
+        };
+        if (!cull) {   // a small world: wave p's one batch, unconditionally
+            for (int i0 = part * MWB_SEG_GROUP; i0 < ns; i0 += MWB_SEG_GROUP * STEP_PARTS) test_batch(i0);
+        }
+        for (int c0 = 0; cull && c0 < NG; c0 += STEP_PARTS * STEP_BOXES) {   // block-uniform trip count (one pass up to 256 segments): barriers inside
+            if (c0 > 0) {   // a larger world: the next boxes
+#pragma unroll
+                for (int j = 0; j < STEP_BOXES; j++) {
+                    const int g = c0 + part + j * STEP_PARTS < NG ? c0 + part + j * STEP_PARTS : 0;
+#pragma unroll
+                    for (int c = 0; c < 4; c++) bb[j][c] = mover ? d.seg_box[(size_t)(g * 4 + c) * segN + e] : 0.0f;
+                }
+            }
+            unsigned near = 0;
+#pragma unroll
+            for (int j = 0; j < STEP_BOXES; j++)
+                if (c0 + part + j * STEP_PARTS < ng && (d.no_seg_cull || mwb_seg_box_near(bb[j][0], bb[j][1], bb[j][2], bb[j][3], px, pz, guard))) near |= 1u << j;
+            s_near[part][lane] = (uint8_t)near;
+            __syncthreads();
+            unsigned todo = 0;   // bit p * STEP_BOXES + j: group c0 + p + j * STEP_PARTS
+            if (mover) {
+#pragma unroll
+                for (int p = 0; p < STEP_PARTS; p++) todo |= (unsigned)s_near[p][lane] << (p * STEP_BOXES);
+            }
+            for (int k = 0; k < part && todo; k++) todo &= todo - 1;   // this wave's first is the part-th of them
+            while (todo) {
+                const int b = __ffs(todo) - 1;
+                for (int k = 0; k < STEP_PARTS && todo; k++) todo &= todo - 1;   // its next one is STEP_PARTS further on
+                test_batch((c0 + b / STEP_BOXES + (b % STEP_BOXES) * STEP_PARTS) * MWB_SEG_GROUP);
+            }
+            if (c0 + STEP_PARTS * STEP_BOXES < NG) __syncthreads();   // s_near is written again
         }
         if (hit) s_hit[lane] = 1;   // every writer stores the same value
     }
@@ -294,15 +373,7 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
     // wall test: walls (all segments, serial: only the carried-entity and pickup tests come here), then the entities
     // in list order except `self_idx` (a box index, or NB for the agent).  Returns 0 none, 1 wall, 2 + k entity k.
     auto intersect_serial = [&](int self_idx, double px, double pz, double radius, bool test_walls) {
-        if (test_walls) {
-            const int ns = d.n_segs[e];
-            for (int i = 0; i < ns; i++) {
-                double q[4];
-#pragma unroll
-                for (int c = 0; c < 4; c++) q[c] = d.segs[(size_t)(i * 4 + c) * d.N + e];
-                if (seg_hit(q, px, pz, radius)) return 1;
-            }
-        }
+        if (test_walls && walls_hit_serial(d, e, d.n_segs[e], px, pz, radius)) return 1;
         int res = 0;
 #pragma unroll
         for (int b = NBX - 1; b >= 0; b--) {   // descending, so that the lowest index wins
@@ -475,15 +546,7 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
         fwd_drift = g.uniform(d.params[MWB_P_FORWARD_DRIFT].lo[0], d.params[MWB_P_FORWARD_DRIFT].hi[0]);
         turn_step = g.uniform(d.params[MWB_P_TURN_STEP].lo[0], d.params[MWB_P_TURN_STEP].hi[0]);
     }
-    auto walls_hit = [&](double px, double pz, double radius) {
-        for (int i = 0; i < ns; i++) {
-            double q[4];
-#pragma unroll
-            for (int c = 0; c < 4; c++) q[c] = d.segs[(size_t)(i * 4 + c) * N + e];
-            if (seg_hit(q, px, pz, radius)) return true;
-        }
-        return false;
-    };
+    auto walls_hit = [&](double px, double pz, double radius) { return walls_hit_serial(d, e, ns, px, pz, radius); };
     // MiniWorldEnv.intersect(ent, pos, radius), miniworld.py:933-959: 0 none, 1 wall, 2 + slot entity, 2 + E the agent
     auto intersect = [&](int self_slot, double px, double pz, double radius, bool rf32) {
         if (walls_hit(px, pz, radius)) return 1;
@@ -1586,6 +1649,13 @@ __global__ void __launch_bounds__(WAVE) reset_kernel(MwbDev d) {
         d.n_segs[e] = w.n_segs;
     }
     for (int i = lane; i < w.n_segs * 4; i += WAVE) d.segs[(size_t)i * d.N + e] = segs[i];   // transposed, see step_kernel
+    if (d.seg_rows) for (int i = lane; i < w.n_segs * 4; i += WAVE) d.seg_rows[(size_t)e * d.S_max * 4 + i] = segs[i];   // env-major twin (culled worlds)
+    for (int g = lane; g < mwb_seg_groups(w.n_segs); g += WAVE) {   // and the groups' boxes, which the step kernels read first (mwb_seg_groups.h)
+        const int n = w.n_segs - g * MWB_SEG_GROUP;
+        const MwbSegBox b = mwb_seg_group_box(segs + g * MWB_SEG_GROUP * 4, n < MWB_SEG_GROUP ? n : MWB_SEG_GROUP);
+        float *o = d.seg_box + (size_t)g * 4 * d.N + e;
+        o[0] = b.min_x; o[(size_t)d.N] = b.min_z; o[2 * (size_t)d.N] = b.max_x; o[3 * (size_t)d.N] = b.max_z;
+    }
     float *grooms = d.rooms + (size_t)e * d.R_max * d.room_words;
     // A room whose outline runs the other way round (the connectors connect_rooms builds between YMaze's hub and arms:
     // miniworld.py:826 lists their corners clockwise there) has every polygon facing away from its inside - with back-face
@@ -4052,12 +4122,7 @@ __global__ void intersect_kernel(MwbDev d, int e, int ent, double x, double z, d
     // MiniWorldEnv.intersect(ent, pos, radius), miniworld.py:933-959: walls, then the entities in list order
     // (boxes, agent) except `ent` itself
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int ns = d.n_segs[e], res = 0;
-    for (int i = 0; i < ns && !res; i++) {
-        double q[4];
-        for (int c = 0; c < 4; c++) q[c] = d.segs[(size_t)(i * 4 + c) * d.N + e];
-        if (seg_hit(q, x, z, radius)) res = 1;
-    }
+    int res = walls_hit_serial(d, e, d.n_segs[e], x, z, radius) ? 1 : 0;
     if (d.ent_task) {   // the entity list in its current order, radii from the entities (tagged sums: the query radius is a Python float)
         const uint8_t *ord = d.ent_order + (size_t)e * MWB_ORDER_STRIDE;
         const int n_ord = d.n_order[e];
