@@ -84,6 +84,7 @@ EXPORTS = [
     "mwb_copy_envs", "mwb_copy_rejected", "mwb_copy_env_bytes",
     "mwb_step_repeat", "mwb_repeat_taken",
     "mwb_rollout_enable", "mwb_rollout_push", "mwb_rollout_gather", "mwb_rollout_after_update", "mwb_rollout_info", "mwb_rollout_rejected",
+    "mwb_bulk_variant",
 ]
 
 _lib = None
@@ -155,6 +156,8 @@ def load():
     L.mwb_rollout_after_update.argtypes = [vp, vp]
     L.mwb_rollout_info.argtypes = [vp, ctypes.POINTER(MwbRolloutInfo)]
     L.mwb_rollout_rejected.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
+    if hasattr(L, "mwb_bulk_variant"):   # (an older library loaded through MWB_LIB for a kernel A/B has none; build() checks EXPORTS)
+        L.mwb_bulk_variant.argtypes = [vp]
     L.mwb_timing_read.argtypes = [vp] +[ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(i32)]
     if L.mwb_abi_version() != ABI_VERSION:
         raise MwbError("libmwbatch.so ABI version mismatch")

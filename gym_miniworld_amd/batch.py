@@ -742,6 +742,12 @@ class BatchedMiniWorld:
         _lib.check(self.L.mwb_frame_reuse_stats(self.h, out))
         return int(out[0]), int(out[1])
 
+    def bulk_variant(self):
+        """1 if the bulk render launch of step() runs the kernel compiled for 80 x 60 frames (render_fixed_kernel), 0 if the
+        generic one (mwb_bulk_variant): the same frames either way.  MWB_NO_FIXED=1 in the environment when the batch is
+        created keeps the generic kernel."""
+        return int(self.L.mwb_bulk_variant(self.h))
+
     def timing_enable(self, on=True):
         """on: False / True, or an int n > 1 to time every n-th pass only (the events cost ~20 us per pass)."""
         _lib.check(self.L.mwb_timing_enable(self.h, int(on)))

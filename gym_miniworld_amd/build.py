@@ -17,7 +17,11 @@ OUT = os.path.join(HERE, "libmwbatch.so")
 REMARKS = os.path.join(HERE, "libmwbatch.resources.txt")
 # -ffp-contract=off: world generation / step must reproduce the reference's float64 arithmetic bit
 # for bit, and the render spec states every fused multiply-add explicitly
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall",
+# -fno-slp-vectorize (every translation unit): left to itself the compiler packs the render kernels' shading arithmetic into
+# v_pk_*_f32 - 322 packed ops in the maze bulk kernel - which occupy the SIMD like two plain ops each and need aligned register
+# pairs (moves, more SGPR reloads, scratch in the POLY / two-box / six-box bulk kernels).  Same IEEE results, contraction stays
+# off; measured in profiles/render_fixed_ab.txt
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-slp-vectorize", "-Wall",
          "-Wno-unused-value"]
 
 

@@ -85,6 +85,7 @@ struct mwb_handle {
     float4 *mesh_data_dev = nullptr;
     MwbMeshDesc *mesh_desc_dev = nullptr;
     float *view_frame = nullptr;   // frame constants of mwb_render_view's size (lazily allocated)
+    bool bulk_fixed = false;     // a step's bulk launch takes render_fixed_kernel (mwb_bulk_fixed_ok at creation and not MWB_NO_FIXED=1); grey output still overrides
     bool frame_reuse = false;    // the last-frame cache exists and step passes copy from it (off: MWB_NO_FRAME_REUSE=1, or frames rendered in tiles)
     // ---- mwb_copy_envs (all of its scratch lives here, none in MwbDev); allocated by the first copy that needs it
     unsigned long long serial = 0;      // unique per mwb_create: the key of another handle's cached descriptor table
@@ -293,6 +294,8 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
     }
     // last-frame reuse: N x (W*H*3 [+ W*H*4 with depth]) bytes of cache and two flags per env; MWB_NO_FRAME_REUSE=1 turns it off
     { const char *no = getenv("MWB_NO_FRAME_REUSE"); h->frame_reuse = !(no && atoi(no)) && d.tile_w == 0; }
+    // the step's bulk launch with the frame's shape compiled in (render_fixed_kernel); MWB_NO_FIXED=1 keeps the generic kernel
+    { const char *no = getenv("MWB_NO_FIXED"); h->bulk_fixed = !(no && atoi(no)) && mwb_bulk_fixed_ok(d); }
 
     // device memory: the per-env arrays from their list (mwb_internal.h), then what is not per env
     const size_t N = (size_t)d.N;
@@ -568,7 +571,7 @@ static int render_tail(mwb_handle *h, int mode, hipStream_t s) {
     mwb_launch_prep(h->dev, mode, s);
     int rc = check_launch("prep_kernel"); if (rc) return rc;
     TMARK(3);
-    mwb_launch_render(h->dev, mode, s);
+    mwb_launch_render(h->dev, mode, s, mode == 2 && h->bulk_fixed);   // mode 2: only a step's bulk launch
     rc = check_launch("render_kernel"); if (rc) return rc;
     TMARK(4);
     return MWB_OK;
@@ -1410,6 +1413,12 @@ extern "C" int mwb_frame_reuse_stats(mwb_handle *h, unsigned long long out[2]) {
     HIP_TRY(hipMemset(h->dev.reuse_stats, 0, 2 * sizeof(unsigned long long)));
     HIP_TRY(hipDeviceSynchronize());
     return MWB_OK;
+}
+
+/* which kernel a step's bulk render launch of this handle runs now: 0 generic (render_kernel / render_grey_kernel), 1 render_fixed_kernel */
+extern "C" int mwb_bulk_variant(mwb_handle *h) {
+    if (!h) return 0;
+    return h->bulk_fixed && h->overlap_reset && !h->dev.grey ? 1 : 0;
 }
 
 extern "C" int mwb_set_domain_rand(mwb_handle *h, int domain_rand) {

@@ -379,7 +379,9 @@ void mwb_view_tile(int *w, int *h);   // the tile mwb_render_view (and large obs
 void mwb_launch_reset(const MwbDev &d, int max_blocks, hipStream_t s);   // grid-strides over reset_list
 // mode 0: every env; 1: only envs with reset_set; 2: only envs without (lets reset overlap the bulk render)
 void mwb_launch_prep(const MwbDev &d, int mode, hipStream_t s);
-void mwb_launch_render(const MwbDev &d, int mode, hipStream_t s);
+// fixed: a step's bulk launch (mode 2) may take render_fixed_kernel where mwb_bulk_fixed_ok(d) holds and no grey output is on
+void mwb_launch_render(const MwbDev &d, int mode, hipStream_t s, bool fixed = false);
+bool mwb_bulk_fixed_ok(const MwbDev &d);   // default observation size, no MWB_DEBUG / MWB_EXP bit, a box task, whole frames
 // cpf: channel planes per frame - 3 (fed from d.obs), or 1 (a grey stack, f32 only: fed from d.grey)
 void mwb_launch_stack(const MwbDev &d, void *stack, int nstack, int dtype, int after_reset, hipStream_t s, int cpf = 3);
 void mwb_launch_stack_slide(const MwbDev &d, void *stack, int nstack, int planes, int dtype, int pos, int from, int mode, hipStream_t s, int cpf = 3);

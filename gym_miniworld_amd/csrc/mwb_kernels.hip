@@ -2485,7 +2485,31 @@ __device__ __forceinline__ bool plane_texcoord(int axis, float plane, float u_or
     return od != 0.0f && tt > 0.0f;
 }
 
-template <int NBOX, bool POLY>
+// Shape policy of render_env / RenderCtx: where a frame's size, layout, "has depth" and the MWB_DEBUG / MWB_EXP words come from.
+// ShapeRuntime reads them from the handle (every render_kernel / render_grey_kernel / render_view_kernel instantiation);
+// ShapeFixed makes them compile-time constants (render_fixed_kernel: the step's bulk launch of handles with the default
+// observation and no switches set), so that the tests on them, their spilled copies and the 64-bit address products disappear.
+struct ShapeRuntime {
+    __device__ __forceinline__ static int width(const MwbDev &d) { return d.W; }
+    __device__ __forceinline__ static int height(const MwbDev &d) { return d.H; }
+    __device__ __forceinline__ static int layout(const MwbDev &d) { return d.layout; }
+    __device__ __forceinline__ static int want_depth(const MwbDev &d) { return d.want_depth; }
+    __device__ __forceinline__ static int debug(const MwbDev &d) { return d.debug_flags; }
+    __device__ __forceinline__ static int exp(const MwbDev &d) { return d.exp_flags; }
+    __device__ __forceinline__ static bool has_depth(const float *depth) { return depth != nullptr; }
+};
+template <int W_, int H_, int LAYOUT, bool DEPTH>
+struct ShapeFixed {
+    __device__ __forceinline__ static constexpr int width(const MwbDev &) { return W_; }
+    __device__ __forceinline__ static constexpr int height(const MwbDev &) { return H_; }
+    __device__ __forceinline__ static constexpr int layout(const MwbDev &) { return LAYOUT; }
+    __device__ __forceinline__ static constexpr int want_depth(const MwbDev &) { return DEPTH ? 1 : 0; }
+    __device__ __forceinline__ static constexpr int debug(const MwbDev &) { return 0; }
+    __device__ __forceinline__ static constexpr int exp(const MwbDev &) { return 0; }
+    __device__ __forceinline__ static constexpr bool has_depth(const float *) { return DEPTH; }
+};
+
+template <int NBOX, bool POLY, class SP = ShapeRuntime>
 struct RenderCtx {
     const float *rooms, *fc;
     const TexLds *tex;
@@ -2873,7 +2897,7 @@ struct RenderCtx {
             const int plane = W * H;
             p[0] = out[0]; p[plane] = out[1]; p[2 * plane] = out[2];
         }
-        if (depth) {
+        if (SP::has_depth(depth)) {
             int z16 = 65535;   // DEPTH_COMPONENT16 of sample 0; cleared to 1.0 where nothing was drawn
             if (s0_drawn) {
                 float zndc = zA - zB / t_s0;
@@ -3234,7 +3258,7 @@ struct RenderCtx {
         float col[3];
         shade<true>(key, 0, cx, cy, col);
         float t_s0 = 1.0f;
-        if (depth) {   // sample 0's ray meets the known surface at the distance the traversal would report
+        if (SP::has_depth(depth)) {   // sample 0's ray meets the known surface at the distance the traversal would report
             float dv[3];
             make_ray(cam, cx + c_sample_x[0], cy + c_sample_y[0], dv);
             const uint32_t kind = key & 7u, side = (key >> 3) & 7u;
@@ -3387,14 +3411,14 @@ __device__ __forceinline__ void reuse_frame(const MwbDev &d, const int e) {
 // reference's 800 x 600 human view, or any observation size whose frame does not fit LDS): everything below works in tile-local
 // pixel coordinates; only the camera's window mapping carries the offset - (2 (wx + ox) - W) / W = (2 wx - (W - 2 ox)) / W, exact
 // in float32 - and the tile's rows go to their places in the big frame.
-template <int THREADS, int NBOX, bool LOOPED, bool POLY, bool TILED = false, bool GREY = false>
+template <int THREADS, int NBOX, bool LOOPED, bool POLY, bool TILED = false, bool GREY = false, class SP = ShapeRuntime>
 __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const int part, unsigned char *smem, const int tx0 = 0,
                                            const int ty0 = 0, const int tw = 0, const int th = 0) {
     // LOOPED (the body sits in a loop over the regenerated-env list): make the lane id opaque to the optimiser so that
     // nothing derived from it is hoisted out of that loop and kept alive across whole frames (200 -> 76 B/lane of scratch)
     int tid = threadIdx.x;
     if (LOOPED) asm volatile("" : "+v"(tid));
-    const int W = TILED ? tw : d.W, H = TILED ? th : d.H;
+    const int W = TILED ? tw : SP::width(d), H = TILED ? th : SP::height(d);
     int n_rooms = d.n_rrooms[e];
     if (n_rooms < 0) n_rooms = 0;
     // The regions of RenderLds (mwb_lds_layout.h), in its order and stepped by its RL_*_BYTES sizes, but as a pointer chain of this
@@ -3434,20 +3458,20 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
             if (tid < MWB_NUM_MESHES) { const MwbMeshDesc &m = d.mesh_desc[tid]; mdesc[tid] = make_uint4(m.node_off, m.tri_off, (uint32_t)m.n_nodes, (uint32_t)m.n_orders); }
     }
     __syncthreads();
-    RenderCtx<NBOX, POLY> ctx;
+    RenderCtx<NBOX, POLY, SP> ctx;
     ctx.rooms = rooms; ctx.fc = fc; ctx.tex = tex; ctx.texels = d.texels; ctx.fb = fb;
     ctx.mesh_desc = d.mesh_desc; ctx.mesh_data = d.mesh_data; ctx.mdesc = mdesc;
     ctx.mb_slots = (unsigned long long *)(mb_base + MB_SLOTS_OFF); ctx.mb_tasks = (uint16_t *)(mb_base + MB_PAIRS_OFF);
     ctx.mb_pix = (uint32_t *)(mb_base + MB_PIX_OFF); ctx.mb_count = (int *)(mb_base + MB_COUNT_OFF);
-    ctx.exp_flags = d.exp_flags; ctx.mesh_slots = 0; ctx.dbg_counters = d.dbg_counters;
+    ctx.exp_flags = SP::exp(d); ctx.mesh_slots = 0; ctx.dbg_counters = d.dbg_counters;
     if constexpr (NBOX > MWB_MAX_BOXES) {   // which slots hold a mesh in this frame
         uint32_t ms = 0;
         for (int bi = 0; bi < d.n_boxes; bi++) ms |= fc[bi * FC_BOX_STRIDE + FC_BOX_HX] == -1.0f ? 1u << bi : 0u;
         ctx.mesh_slots = (uint32_t)__builtin_amdgcn_readfirstlane((int)ms);
     }
-    ctx.depth = d.want_depth ? d.depth + (size_t)e * d.W * d.H + (TILED ? (size_t)ty0 * d.W + tx0 : 0) : nullptr;
-    ctx.depth_stride = TILED ? d.W : W;
-    ctx.n_rooms = n_rooms; ctx.W = W; ctx.H = H; ctx.layout = d.layout;
+    ctx.depth = SP::want_depth(d) ? d.depth + (size_t)e * SP::width(d) * SP::height(d) + (TILED ? (size_t)ty0 * SP::width(d) + tx0 : 0) : nullptr;
+    ctx.depth_stride = TILED ? SP::width(d) : W;
+    ctx.n_rooms = n_rooms; ctx.W = W; ctx.H = H; ctx.layout = SP::layout(d);
     Cam &cam = ctx.cam;
     // frame constants are workgroup-uniform: pin them to scalar registers
     auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
@@ -3456,8 +3480,8 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
     cam.TW = uni(fc[FC_TW]); cam.TH = uni(fc[FC_TH]);
     cam.Wf = (float)W; cam.Hf = (float)H; cam.invW = 1.0f / (float)W; cam.invH = 1.0f / (float)H;
     if (TILED) {   // window x of tile column c = tx0 + c; window y (up) of tile row r (from the top) = (d.H - ty0 - th) + (th - r)
-        cam.Wf = (float)(d.W - 2 * tx0); cam.Hf = (float)(d.H - 2 * (d.H - ty0 - th));
-        cam.invW = 1.0f / (float)d.W; cam.invH = 1.0f / (float)d.H;
+        cam.Wf = (float)(SP::width(d) - 2 * tx0); cam.Hf = (float)(SP::height(d) - 2 * (SP::height(d) - ty0 - th));
+        cam.invW = 1.0f / (float)SP::width(d); cam.invH = 1.0f / (float)SP::height(d);
     }
     // room containing the eye: first (lowest index) rectangle that holds it, bounds inclusive.  Every wave finds it for
     // itself (64 rooms per sweep, lowest set bit of the first non-empty ballot): no LDS atomic, no barrier
@@ -3490,7 +3514,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
         cull_cc_px[0] = uni(fc[FC_CULL_CC_PIXEL]);
     }
     ctx.boxes_in_view = __builtin_amdgcn_readfirstlane(__float_as_int(fc[FC_BOX_IN_VIEW])) != 0;
-    ctx.item_res = (d.debug_flags & (1 | 32 | 128)) ? nullptr : item_res;   // filled by the lattice pass below
+    ctx.item_res = (SP::debug(d) & (1 | 32 | 128)) ? nullptr : item_res;   // filled by the lattice pass below
     ctx.part_h_inv = 65536 / ((H + 3) / 4) + 1;
 
     // Pass structure per wave: a 16 x 4 grid of rays through PIXEL CORNERS per pass, marching down a
@@ -3510,7 +3534,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
     // (as many bits as 16 - the coordinate bits leave, at most 3; MWB_DEBUG bit 3: none)
     const int hshift = mwb_coord_bits(H);
     const int qshift = wshift + hshift, hmask = (1 << hshift) - 1;
-    const int skip_max = (d.debug_flags & 8) || qshift >= 16 ? 0 : (1 << (16 - qshift > 3 ? 3 : 16 - qshift)) - 1;
+    const int skip_max = (SP::debug(d) & 8) || qshift >= 16 ? 0 : (1 << (16 - qshift > 3 ? 3 : 16 - qshift)) - 1;
     uint16_t *queue = queues + wave * QUEUE_CAP;
     uint32_t *iq_key = ikeys + wave * QUEUE_CAP;
     uint16_t *iq_pix = ipix + wave * QUEUE_CAP;
@@ -3523,7 +3547,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
     // none wasted).  Waves take them from an LDS counter as they become free, so a wave that drew cheap
     // (uniform) items does not idle while another one works through the edge-rich ones.
     const int part_h = (H + 3) / 4;                       // pixel rows per item
-    const bool split_x = d.layout == MWB_LAYOUT_CWH;
+    const bool split_x = SP::layout(d) == MWB_LAYOUT_CWH;
     const int half_strips = (n_strips + 1) / 2;
     const int n_items = part < 0 ? n_strips * 4
                                  : (split_x ? (part == 0 ? half_strips : n_strips - half_strips) * 4 : n_strips * 2);
@@ -3587,7 +3611,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
             if (mq_count > MQ_CAP - WAVE) {
                 mq_count -= WAVE;
                 const int q = mqueue[mq_count + lane];
-                if (!(d.debug_flags & 2)) ctx.pixels_mesh(q & wmask, (q >> wshift) & hmask, q >> qshift, true);
+                if (!(SP::debug(d) & 2)) ctx.pixels_mesh(q & wmask, (q >> wshift) & hmask, q >> qshift, true);
             }
         }
         const unsigned long long em = __ballot(edge);
@@ -3602,12 +3626,12 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
         if (iq_count >= WAVE) {
             iq_count -= WAVE;
             const int q = iq_pix[iq_count + lane];
-            if (!(d.debug_flags & 4)) ctx.pixel_interior(q & wmask, q >> wshift, iq_key[iq_count + lane]);
+            if (!(SP::debug(d) & 4)) ctx.pixel_interior(q & wmask, q >> wshift, iq_key[iq_count + lane]);
         }
         if (q_count >= WAVE) {
             q_count -= WAVE;
             const int q = queue[q_count + lane];
-            if (!(d.debug_flags & 2)) ctx.pixel_full(q & wmask, (q >> wshift) & hmask, q >> qshift);
+            if (!(SP::debug(d) & 2)) ctx.pixel_full(q & wmask, (q >> wshift) & hmask, q >> qshift);
         }
     };
     // Item pre-tests, all at once.  If the corner rays of a screen rectangle reach the same convex piece of a room surface
@@ -3617,7 +3641,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
     // traced ONCE per frame by waves 0 and 1 (8 lattice columns = 7 strips per pass) - neighbouring items share corners,
     // and a wave that pulls an item finds the verdict in LDS instead of spending a whole wave-trace on 8 rays.
     // A uniform item skips its 4 corner passes, a uniform half leaves 2.
-    if (!(d.debug_flags & (1 | 32 | 128))) {
+    if (!(SP::debug(d) & (1 | 32 | 128))) {
         for (int chunk0 = 0; chunk0 < n_strips; chunk0 += 7) {
             if (wave < 2) {
                 const int r = lane >> 3, k = lane & 7, q = wave * 2 + (r >> 2), rr = r & 3;
@@ -3658,7 +3682,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
                 const int c1 = common_crossings(path_raw, __shfl(path_raw, (lane + 24) & (WAVE - 1)));
                 const int c2 = common_crossings(path_raw, __shfl(path_raw, (lane + 25) & (WAVE - 1)));
                 common = common < c1 ? common : c1; common = common < c2 ? common : c2;
-                if ((d.debug_flags & 8) || ctx.cam_room < 0) common = 0;
+                if ((SP::debug(d) & 8) || ctx.cam_room < 0) common = 0;
                 int item_room = ctx.cam_room;
                 if (common > 0) {
                     const int r = POLY ? walk_rooms_poly(rooms, ctx.cam_room, cam.eye, dv, common) : walk_rooms(rooms, ctx.cam_room, cam.eye, dv, common);
@@ -3723,8 +3747,8 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
         int prow0 = row0, prows = rows;   // the rows left for the per-pixel corner passes
         int item_skip = 0, item_room = ctx.cam_room;
         uint32_t item_boxes = 0xFFFFFFFFu;   // the boxes whose pixel-inflated sphere can meet the item's rays
-        if (d.debug_flags & 128) continue;   // experiment: prologue + copy-out only
-        if (!(d.debug_flags & (1 | 32))) {
+        if (SP::debug(d) & 128) continue;   // experiment: prologue + copy-out only
+        if (!(SP::debug(d) & (1 | 32))) {
             const int wi = (W - x0) < (TILE_CX - 1) ? (W - x0) : (TILE_CX - 1);   // pixel columns of this item
             const uint4 res = item_res[item];   // the frame-level pre-test's verdict (workgroup-uniform address)
             const uint32_t ukey = (uint32_t)__builtin_amdgcn_readfirstlane((int)res.x);
@@ -3749,7 +3773,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
             }
             if (prows <= 0) continue;
         }
-        if (d.debug_flags & 64) continue;   // experiment: no per-pixel corner passes (prologue + pre-test + copy-out only)
+        if (SP::debug(d) & 64) continue;   // experiment: no per-pixel corner passes (prologue + pre-test + copy-out only)
         const int n_pass_i = (prows + 1 + TILE_CY - 1) / TILE_CY;   // corner rows of the remaining rows: prows + 1
         uint32_t prev_key = 0, prev_path = 0;
         for (int p = 0; p < n_pass_i; p++) {
@@ -3773,7 +3797,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
             prev_key = key; prev_path = path;
             const int px = x0 + ci, py = crow - 1;
             const bool is_pixel = ci < TILE_CX - 1 && px < W && py >= prow0 && py < prow0 + prows && !(p == 0 && cj == 0);
-            bool interior = !(d.debug_flags & 1) && is_pixel && ok && key == k_br && key == k_tl && key == k_tr &&
+            bool interior = !(SP::debug(d) & 1) && is_pixel && ok && key == k_br && key == k_tl && key == k_tr &&
                             path == p_br && path == p_tl && path == p_tr;
             if (interior && ctx.boxes_in_view && box_may_touch(px, py, item_boxes)) interior = false;
             int skip = common_crossings4(path, p_br, p_tl, p_tr) + item_skip;
@@ -3788,7 +3812,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
     if (lane == 0) { left[wave] = iq_count; left[n_waves + wave] = q_count; }
     if constexpr (NBOX > MWB_MAX_BOXES) { if (lane == 0) mleft[wave] = mq_count; }
     __syncthreads();
-    if (!(d.debug_flags & 4)) {
+    if (!(SP::debug(d) & 4)) {
         int g = tid, owner = -1;
 #pragma unroll
         for (int w = 0; w < THREADS / WAVE; w++) {
@@ -3800,7 +3824,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
             ctx.pixel_interior(p & wmask, p >> wshift, ikeys[owner * QUEUE_CAP + g]);
         }
     }
-    if (!(d.debug_flags & 2)) {
+    if (!(SP::debug(d) & 2)) {
         int g = THREADS - 1 - tid, owner = -1;
 #pragma unroll
         for (int w = 0; w < THREADS / WAVE; w++) {
@@ -3813,7 +3837,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
         }
     }
     if constexpr (NBOX > MWB_MAX_BOXES) {
-        if (!(d.debug_flags & 2)) {   // the mesh pixels, pooled the same way: 64-pixel batches dealt out to the waves in turn
+        if (!(SP::debug(d) & 2)) {   // the mesh pixels, pooled the same way: 64-pixel batches dealt out to the waves in turn
             int total = 0;
 #pragma unroll
             for (int w = 0; w < THREADS / WAVE; w++) total += mleft[w];
@@ -3839,20 +3863,20 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
         uint8_t *keep = (!TILED && !LOOPED && d.frame_cache) ? d.frame_cache + (size_t)e * nbytes : nullptr;
         // The depth map went to HBM pixel by pixel (RenderCtx is full): the cache gets this workgroup's part of it read back - its
         // own waves' stores, ordered before these loads by the barrier above.  [H][W] floats whatever the frame's layout.
-        const uint8_t *zsrc = (keep && d.want_depth) ? (const uint8_t *)(d.depth + (size_t)e * W * H) : nullptr;
+        const uint8_t *zsrc = (keep && SP::want_depth(d)) ? (const uint8_t *)(d.depth + (size_t)e * W * H) : nullptr;
         uint8_t *zkeep = zsrc ? (uint8_t *)(d.depth_cache + (size_t)e * W * H) : nullptr;
         if (TILED) {
-            if (d.layout == MWB_LAYOUT_HWC) {   // the tile's rows into the big frame
-                uint8_t *big = d.obs + ((size_t)e * d.W * d.H + (size_t)ty0 * d.W + tx0) * 3;
+            if (SP::layout(d) == MWB_LAYOUT_HWC) {   // the tile's rows into the big frame
+                uint8_t *big = d.obs + ((size_t)e * SP::width(d) * SP::height(d) + (size_t)ty0 * SP::width(d) + tx0) * 3;
                 for (int i = tid; i < H * W * 3; i += THREADS) {
                     const int row = i / (W * 3), col = i - row * (W * 3);
-                    big[(size_t)row * d.W * 3 + col] = fb[i];
+                    big[(size_t)row * SP::width(d) * 3 + col] = fb[i];
                 }
             } else {   // CWH: the tile is [3][W][H] in LDS, its columns go into the planes [3][d.W][d.H]
-                uint8_t *big = d.obs + (size_t)e * d.W * d.H * 3;
+                uint8_t *big = d.obs + (size_t)e * SP::width(d) * SP::height(d) * 3;
                 for (int i = tid; i < H * W * 3; i += THREADS) {
                     const int q = i / (W * H), r = i - q * (W * H), x = r / H, y = r - x * H;
-                    big[((size_t)q * d.W + tx0 + x) * d.H + ty0 + y] = fb[i];
+                    big[((size_t)q * SP::width(d) + tx0 + x) * SP::height(d) + ty0 + y] = fb[i];
                 }
             }
         } else if (part < 0) {
@@ -3879,7 +3903,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
         // Fused frame stack (mwb_stack_enable with MWB_STACK_FUSED; CWH frames): the new frame also goes straight into the
         // newest three planes of the env's sliding window - u8 -> f32 on the way out of LDS - and an env that was
         // regenerated in this pass gets its history planes zeroed (VecPyTorchFrameStack, envs.py:149-156): no stack pass.
-        if (d.stk && d.layout == MWB_LAYOUT_CWH) {
+        if (d.stk && SP::layout(d) == MWB_LAYOUT_CWH) {
             const int plane = W * H, C = d.stk_C;
             const int cpf = GREY ? d.stk_cpf : 3;   // planes per frame: a grey stack (1) exists only behind the GREY instantiations
             const size_t env_base = ((size_t)e * d.stk_K + d.stk_pos) * plane;   // first element of the window
@@ -3913,7 +3937,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
 // 2: all the others (bulk).  A template parameter so that the three launches carry distinct kernel names
 // in profiles.
 // NBOX = MWB_MAX_ENTS: the entity tasks' instantiation (mesh BVH walks, frames): 4 workgroups per CU (128 VGPRs) instead of 5
-template <int THREADS, int MODE, int NBOX, bool POLY, bool GREY>
+template <int THREADS, int MODE, int NBOX, bool POLY, bool GREY, class SP = ShapeRuntime>
 __device__ __forceinline__ void render_body(const MwbDev &d, unsigned char *smem) {
     if (MODE == 1) {
         __builtin_amdgcn_s_setprio(3);   // the few regenerated envs, beside the bulk render (see reset_kernel)
@@ -3963,7 +3987,7 @@ __device__ __forceinline__ void render_body(const MwbDev &d, unsigned char *smem
             }
         }
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();   // read by every wave: stays in scalar registers
-        render_env<THREADS, NBOX, false, POLY, false, GREY>(d, e, part, smem);
+        render_env<THREADS, NBOX, false, POLY, false, GREY, SP>(d, e, part, smem);
         if (threadIdx.x == 0) {
             const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
             if (d.wg_ts) { d.wg_ts[2 * b] = t0; d.wg_ts[2 * b + 1] = t1; }
@@ -3987,6 +4011,17 @@ template <int THREADS, int MODE, int NBOX, bool POLY = false>
 __global__ void __launch_bounds__(THREADS, NBOX > MWB_MAX_BOXES ? ENT_WGS_PER_CU : 5) render_grey_kernel(MwbDev d) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     render_body<THREADS, MODE, NBOX, POLY, true>(d, smem);
+}
+// A step's bulk launch (MODE 2) of a box task at the default observation size with no MWB_DEBUG / MWB_EXP bit set and no grey
+// output: render_env compiled under ShapeFixed - the frame's size, layout and "has depth" are constants, the debug tests are
+// gone.  Same LDS layout, launch bounds and work lists as render_kernel<256, 2, NBOX, POLY>, and the same results bit for bit
+// (tests/test_gpu_render_fixed.py); mwb_bulk_fixed_ok decides on the host, MWB_NO_FIXED=1 keeps the generic kernel.
+#define MWB_FIXED_W 80
+#define MWB_FIXED_H 60
+template <int NBOX, bool POLY, int LAYOUT, bool DEPTH>
+__global__ void __launch_bounds__(RENDER_THREADS, 5) render_fixed_kernel(MwbDev d) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    render_body<RENDER_THREADS, 2, NBOX, POLY, false, ShapeFixed<MWB_FIXED_W, MWB_FIXED_H, LAYOUT, DEPTH>>(d, smem);
 }
 
 // The agent's view at any size (mwb_render_view): a grid of tiles per env, one workgroup each.  d.W x d.H is the view's size, d.obs /
@@ -4169,6 +4204,25 @@ static auto with_render_variant(const MwbDev &d, F &&f) {
     if (d.n_boxes == 2) return f(integral_constant<int, 2>{}, std::false_type{});          // the two-box T-maze, SimToRealPush
     return f(integral_constant<int, 1>{}, std::false_type{});
 }
+// May a step's bulk launch of this handle run render_fixed_kernel?  Everything ShapeFixed turns into a constant must hold
+// (grey output is enabled after creation: mwb_launch_render looks at d.grey itself).
+bool mwb_bulk_fixed_ok(const MwbDev &d) {
+    return d.W == MWB_FIXED_W && d.H == MWB_FIXED_H && d.debug_flags == 0 && d.exp_flags == 0 && !d.ent_task && d.tile_w == 0 &&
+           (d.layout == MWB_LAYOUT_HWC || d.layout == MWB_LAYOUT_CWH);
+}
+// ... its render_fixed_kernel instantiation <NBOX, POLY, layout, depth>: f(kernel), a box task's handle only
+typedef void (*render_fixed_fn_t)(MwbDev);
+template <class F>
+static auto with_fixed_kernel(const MwbDev &d, F &&f) {
+    return with_render_variant(d, [&](auto nbox, auto poly) {
+        constexpr int NB = decltype(nbox)::value <= MWB_MAX_BOXES ? decltype(nbox)::value : 1;   // (the entity list has none)
+        constexpr bool PO = decltype(poly)::value;
+        render_fixed_fn_t k;
+        if (d.layout == MWB_LAYOUT_CWH) k = d.want_depth ? render_fixed_kernel<NB, PO, MWB_LAYOUT_CWH, true> : render_fixed_kernel<NB, PO, MWB_LAYOUT_CWH, false>;
+        else k = d.want_depth ? render_fixed_kernel<NB, PO, MWB_LAYOUT_HWC, true> : render_fixed_kernel<NB, PO, MWB_LAYOUT_HWC, false>;
+        return f(k);
+    });
+}
 // ... and a run-time render mode its MODE: f(integral_constant<int, MODE>)
 template <class F>
 static auto with_render_mode(int mode, F &&f) {
@@ -4231,6 +4285,9 @@ int mwb_prepare_kernels(const MwbDev &d) {
             });
             if (err != hipSuccess) return -2;
         }
+    if (q > 64 * 1024 && mwb_bulk_fixed_ok(d) &&
+        with_fixed_kernel(d, [&](render_fixed_fn_t k) { return hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q); }) != hipSuccess)
+        return -2;
     return 0;
 }
 
@@ -4252,7 +4309,7 @@ void mwb_launch_prep(const MwbDev &d, int mode, hipStream_t s) {
     const int blocks = mode == 1 ? 8 : (d.N + 255) / 256 + (mode == 2 && d.tile_w == 0 ? 1 : 0);
     hipLaunchKernelGGL(prep_kernel, dim3(blocks), dim3(256), 0, s, d, mode);
 }
-void mwb_launch_render(const MwbDev &d, int mode, hipStream_t s) {
+void mwb_launch_render(const MwbDev &d, int mode, hipStream_t s, bool fixed) {
     with_render_mode(mode, [&](auto m) {
         constexpr int MODE = decltype(m)::value;
         if (d.tile_w > 0) {   // every frame as a few tiles, one workgroup each (see render_view_kernel): frames too large for one workgroup's LDS
@@ -4261,6 +4318,10 @@ void mwb_launch_render(const MwbDev &d, int mode, hipStream_t s) {
         }
         const dim3 g(MODE == 1 ? (d.N < LIST_GRID ? d.N : LIST_GRID) : d.N + d.split_envs), b(RENDER_THREADS);
         const size_t lds = mwb_render_lds_bytes(d);
+        if (MODE == 2 && fixed && !d.grey && mwb_bulk_fixed_ok(d)) {   // a step's bulk launch, everything ShapeFixed fixes holds
+            with_fixed_kernel(d, [&](render_fixed_fn_t k) { hipLaunchKernelGGL(k, g, b, lds, s, d); return 0; });
+            return;
+        }
         with_render_variant(d, [&](auto nbox, auto poly) {
             if (d.grey) hipLaunchKernelGGL((render_grey_kernel<RENDER_THREADS, MODE, decltype(nbox)::value, decltype(poly)::value>), g, b, lds, s, d);
             else hipLaunchKernelGGL((render_kernel<RENDER_THREADS, MODE, decltype(nbox)::value, decltype(poly)::value>), g, b, lds, s, d);

@@ -283,6 +283,11 @@ int mwb_render(mwb_handle *h, void *stream);
  * environment variable MWB_NO_FRAME_REUSE=1 at mwb_create turns it off (no cache is allocated); it is off as well for frames
  * rendered in tiles.  out: frames the step passes reused / rendered since the last call.  Synchronous. */
 int mwb_frame_reuse_stats(mwb_handle *h, unsigned long long out[2]);
+/* Which kernel the bulk render launch of mwb_step runs for this handle now: 1 = render_fixed_kernel, compiled for 80 x 60
+ * observations with the layout and "has depth" as constants (box tasks, no MWB_DEBUG / MWB_EXP bit set, no grey output, the
+ * side stream in use), 0 = the generic render kernel (every other handle, and mwb_reset / mwb_render / the side stream always).
+ * Both produce the same bytes.  The environment variable MWB_NO_FIXED=1 at mwb_create keeps the generic kernel.  NULL: 0. */
+int mwb_bulk_variant(mwb_handle *h);
 int mwb_get_outputs(mwb_handle *h, mwb_outputs *out);
 
 /* ---- learner-side layout fusion ---------------------------------------- */

@@ -78,11 +78,11 @@ if __name__ == "__main__":
         out_json = args[i + 1]
         del args[i:i + 2]
     table = kernel_resources(args)
-    print("%-64s %5s %5s %5s %8s %4s %7s" % ("kernel", "VGPR", "AGPR", "SGPR", "scratch", "occ", "LDS"))
+    print("%-64s %5s %5s %5s %8s %4s %7s %6s" % ("kernel", "VGPR", "AGPR", "SGPR", "scratch", "occ", "LDS", "sspill"))
     for k, v in sorted(table.items()):
         short = re.sub(r"\(MwbDev.*", "", k)
-        print("%-64s %5d %5d %5d %8d %4d %7d" % (short[:64], v.get("vgprs", -1), v.get("agprs", -1), v.get("sgprs", -1),
-                                                  v.get("scratch", -1), v.get("occupancy", -1), v.get("lds", -1)))
+        print("%-64s %5d %5d %5d %8d %4d %7d %6d" % (short[:64], v.get("vgprs", -1), v.get("agprs", -1), v.get("sgprs", -1),
+                                                      v.get("scratch", -1), v.get("occupancy", -1), v.get("lds", -1), v.get("sgpr_spill", -1)))
     if out_json:
         with open(out_json, "w") as f:
             json.dump(table, f, indent=1, sort_keys=True)
