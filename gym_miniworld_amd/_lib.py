@@ -31,6 +31,7 @@ LAYOUT_HWC, LAYOUT_CWH = 0, 1
 COPY_NO_RENDER = 1   # MWB_COPY_NO_RENDER
 MAX_REPEAT = 64      # MWB_MAX_REPEAT
 ROLLOUT_GREY = 1     # MWB_ROLLOUT_GREY
+RETURNS_DISCOUNTED, RETURNS_GAE, RETURNS_PSI = 0, 1, 2   # MWB_RETURNS_*
 
 
 class MwbConfig(ctypes.Structure):
@@ -74,6 +75,11 @@ class MwbRolloutInfo(ctypes.Structure):   # struct mwb_rollout_info
     ]
 
 
+class MwbRolloutLearnerInfo(ctypes.Structure):   # struct mwb_rollout_learner_info
+    _fields_ = [(n, ctypes.c_void_p) for n in ("action", "log_prob", "value", "taken", "ret", "adv", "psi_ret")] + \
+               [(n + "_bytes", ctypes.c_size_t) for n in ("action", "log_prob", "value", "taken", "ret", "adv", "psi_ret")]
+
+
 EXPORTS = [
     "mwb_create", "mwb_destroy", "mwb_last_error", "mwb_abi_version", "mwb_set_texture", "mwb_seed", "mwb_reset",
     "mwb_step", "mwb_render", "mwb_get_outputs", "mwb_get_state", "mwb_set_agent", "mwb_intersect",
@@ -84,6 +90,7 @@ EXPORTS = [
     "mwb_copy_envs", "mwb_copy_rejected", "mwb_copy_env_bytes",
     "mwb_step_repeat", "mwb_repeat_taken",
     "mwb_rollout_enable", "mwb_rollout_push", "mwb_rollout_gather", "mwb_rollout_after_update", "mwb_rollout_info", "mwb_rollout_rejected",
+    "mwb_rollout_learner_enable", "mwb_rollout_learner_info", "mwb_rollout_insert", "mwb_rollout_returns", "mwb_rollout_gather_cols",
     "mwb_bulk_variant",
 ]
 
@@ -156,6 +163,11 @@ def load():
     L.mwb_rollout_after_update.argtypes = [vp, vp]
     L.mwb_rollout_info.argtypes = [vp, ctypes.POINTER(MwbRolloutInfo)]
     L.mwb_rollout_rejected.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
+    L.mwb_rollout_learner_enable.argtypes = [vp]
+    L.mwb_rollout_learner_info.argtypes = [vp, ctypes.POINTER(MwbRolloutLearnerInfo)]
+    L.mwb_rollout_insert.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mwb_rollout_returns.argtypes = [vp, i32, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp]
+    L.mwb_rollout_gather_cols.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     if hasattr(L, "mwb_bulk_variant"):   # (an older library loaded through MWB_LIB for a kernel A/B has none; build() checks EXPORTS)
         L.mwb_bulk_variant.argtypes = [vp]
     L.mwb_timing_read.argtypes = [vp] +[ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(i32)]

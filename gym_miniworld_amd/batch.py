@@ -128,24 +128,34 @@ def check_repeat_args(repeat, num_envs, n_actions, n_skip=None, n_counts=None, n
     return int(repeat)
 
 
+def _check_index_list(index, limit, what, limit_text):
+    """the shared body of the two checks below -> the list as a one-dimensional int64 array"""
+    a = np.asarray(index)
+    if a.size == 0:
+        raise ValueError("rollout %s: the index list is empty" % what)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("rollout %s: indices must be integers, not %s" % (what, a.dtype))
+    a = a.reshape(-1).astype(np.int64)
+    if (a < 0).any():
+        raise ValueError("rollout %s: negative index %d" % (what, a[a < 0][0]))
+    if (a >= limit).any():
+        raise ValueError("rollout %s: index %d outside [0, %d) = %s" % (what, a[a >= limit][0], limit, limit_text))
+    return a
+
+
 def check_rollout_indices(index, cursor, num_envs):
     """What Rollout.gather refuses before anything is launched, for an index list that lives on the host: raises ValueError for
     an empty list, for indices that are no integers and for an index outside [0, (cursor + 1) * num_envs) - a row the device
     would write as zeros and count (mwb_rollout_rejected).  index[i] = t * num_envs + e, t in 0 .. cursor.  Returns the list as
     a one-dimensional int64 array."""
-    a = np.asarray(index)
-    if a.size == 0:
-        raise ValueError("rollout gather: the index list is empty")
-    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
-        raise ValueError("rollout gather: indices must be integers, not %s" % a.dtype)
-    a = a.reshape(-1).astype(np.int64)
-    if (a < 0).any():
-        raise ValueError("rollout gather: negative index %d" % a[a < 0][0])
-    limit = (int(cursor) + 1) * int(num_envs)
-    if (a >= limit).any():
-        raise ValueError("rollout gather: index %d outside [0, %d) = (cursor + 1) * num_envs with the cursor at %d"
-                         % (a[a >= limit][0], limit, cursor))
-    return a
+    return _check_index_list(index, (int(cursor) + 1) * int(num_envs), "gather", "(cursor + 1) * num_envs with the cursor at %d" % cursor)
+
+
+def check_rollout_column_indices(index, num_steps, num_envs):
+    """What Rollout.minibatch refuses before anything is launched, for an index list that lives on the host: as
+    check_rollout_indices, with the bound of the reference's [:-1] views: index[i] = t * num_envs + e with t in 0 .. num_steps - 1,
+    so an index outside [0, num_steps * num_envs) raises ValueError."""
+    return _check_index_list(index, int(num_steps) * int(num_envs), "minibatch", "num_steps * num_envs")
 
 
 class Rollout:
@@ -154,9 +164,18 @@ class Rollout:
         ro.push(after_reset=True) after reset(), ro.push() after every step()     rollouts.obs[step + 1].copy_(obs) + insert()
         ro.gather(idx)                                                            obs[:-1].view(-1, ...)[idx]
         ro.after_update()                                                         rollouts.after_update()
-    rewards [T, N], masks [T+1, N], features [T+1, N, 2] and ages [T+1, N] are zero-copy views of the library's arrays."""
+    rewards [T, N], masks [T+1, N], features [T+1, N, 2] and ages [T+1, N] are zero-copy views of the library's arrays.
 
-    def __init__(self, batch, num_steps, nstack, grey):
+    With learner=True (or learner_enable()) the rest of RolloutStorage lives here as well (mwb_rollout_learner_enable):
+        ro.insert(value, log_prob, action) after the push                          the small columns of rollouts.insert()
+        ro.compute_returns(next_value, use_gae, gamma, tau)                        rollouts.compute_returns(), one kernel
+        ro.compute_psi_returns(next_psi, gamma)                                    rollouts.compute_psi_returns()
+        ro.feed_forward_generator(advantages, num_mini_batch)                      rollouts.feed_forward_generator()
+    actions [T, N] int64, action_log_probs [T, N], value_preds [T+1, N], returns [T+1, N], advantages [T, N], psi_returns
+    [T+1, N, 2] and taken [T, N] int32 - the sub-steps of every transition, by which the returns discount: gamma ** taken -
+    are zero-copy views too.  The recurrent hidden states stay with the trainer (their width is the policy's)."""
+
+    def __init__(self, batch, num_steps, nstack, grey, learner=False):
         torch = batch.torch
         self.batch, self.L, self.torch = batch, batch.L, torch
         _lib.check(self.L.mwb_rollout_enable(batch.h, int(num_steps), int(nstack), _lib.ROLLOUT_GREY if grey else 0))
@@ -173,6 +192,28 @@ class Rollout:
         self.ages = as_t(info.age, (T + 1, N), "|u1")
         self._arange = torch.arange(N, dtype=torch.int64, device=batch.device)
         self._keep = None
+        self.learner = False
+        if learner:
+            self.learner_enable()
+
+    def learner_enable(self):
+        """Allocate the learner half (mwb_rollout_learner_enable); from now on every push records `taken`"""
+        torch, b = self.torch, self.batch
+        _lib.check(self.L.mwb_rollout_learner_enable(b.h))
+        info = _lib.MwbRolloutLearnerInfo()
+        _lib.check(self.L.mwb_rollout_learner_info(b.h, ctypes.byref(info)))
+        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, b), device=b.device)  # noqa: E731
+        T, N = self.num_steps, self.num_envs
+        self.actions = as_t(info.action, (T, N), "<i8")
+        self.action_log_probs = as_t(info.log_prob, (T, N), "<f4")
+        self.value_preds = as_t(info.value, (T + 1, N), "<f4")
+        self.taken = as_t(info.taken, (T, N), "<i4")
+        self.returns = as_t(info.ret, (T + 1, N), "<f4")
+        self.advantages = as_t(info.adv, (T, N), "<f4")
+        self.psi_returns = as_t(info.psi_ret, (T + 1, N, 2), "<f4")
+        self.nbytes += int(info.action_bytes + info.log_prob_bytes + info.value_bytes + info.taken_bytes + info.ret_bytes
+                           + info.adv_bytes + info.psi_ret_bytes)
+        self.learner = True
 
     def _info(self):
         info = _lib.MwbRolloutInfo()
@@ -230,6 +271,88 @@ class Rollout:
 
     def after_update(self):
         _lib.check(self.L.mwb_rollout_after_update(self.batch.h, self.batch._stream()))
+
+    # ------------------------------------------------------------------------------- the learner half
+    def _column(self, what, x, count, dtypes):
+        """a caller's tensor as the contiguous device array the library reads: ValueError (nothing launched) unless it is a tensor
+        on the batch's device, of one of `dtypes`, with `count` elements"""
+        torch = self.torch
+        if not torch.is_tensor(x) or x.device != self.batch.device:
+            raise ValueError("rollout %s: a tensor on %s is required" % (what, self.batch.device))
+        if x.dtype not in dtypes:
+            raise ValueError("rollout %s: dtype %s, not %s" % (what, " or ".join(str(d) for d in dtypes), x.dtype))
+        if x.numel() != count:
+            raise ValueError("rollout %s: %d elements required, not %d" % (what, count, x.numel()))
+        return x.reshape(-1).contiguous()
+
+    def insert(self, value=None, log_prob=None, action=None):
+        """value_preds[step - 1], action_log_probs[step - 1], actions[step - 1] of the transition that led to the last push
+        (storage.py:57-61); None leaves that column as it is.  float32 [N] or [N, 1]; action int64 or int32."""
+        torch, N = self.torch, self.num_envs
+        v = None if value is None else self._column("insert: value", value, N, (torch.float32,))
+        lp = None if log_prob is None else self._column("insert: log_prob", log_prob, N, (torch.float32,))
+        a = None if action is None else self._column("insert: action", action, N, (torch.int64, torch.int32))
+        ptr = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())   # noqa: E731
+        a64, a32 = (a, None) if a is None or a.dtype == torch.int64 else (None, a)
+        _lib.check(self.L.mwb_rollout_insert(self.batch.h, ptr(a64), ptr(a32), ptr(lp), ptr(v), self.batch._stream()))
+        self._keep_cols = (v, lp, a)   # alive until the asynchronous kernel has consumed them
+
+    def compute_returns(self, next_value, use_gae, gamma, tau, rewards=None):
+        """RolloutStorage.compute_returns (storage.py:82-99) in one kernel, every transition discounted by gamma ** taken: fills
+        returns, advantages (returns - value_preds, ppo.py:33) and value_preds[-1].  rewards [T, N]: read instead of the stored
+        rewards (the sf=True branch's estimated rewards).  The rollout must be full."""
+        torch, N = self.torch, self.num_envs
+        nv = self._column("compute_returns: next_value", next_value, N, (torch.float32,))
+        rw = None if rewards is None else self._column("compute_returns: rewards", rewards, self.num_steps * N, (torch.float32,))
+        _lib.check(self.L.mwb_rollout_returns(self.batch.h, _lib.RETURNS_GAE if use_gae else _lib.RETURNS_DISCOUNTED, float(gamma), float(tau),
+                                              ctypes.c_void_p(nv.data_ptr()), None, None if rw is None else ctypes.c_void_p(rw.data_ptr()),
+                                              self.batch._stream()))
+        self._keep_ret = (nv, rw)
+
+    def compute_psi_returns(self, next_psi, gamma):
+        """RolloutStorage.compute_psi_returns (storage.py:101-105): fills psi_returns from the stored features; next_psi [N, 2]"""
+        np_ = self._column("compute_psi_returns: next_psi", next_psi, 2 * self.num_envs, (self.torch.float32,))
+        _lib.check(self.L.mwb_rollout_returns(self.batch.h, _lib.RETURNS_PSI, float(gamma), 1.0, None, ctypes.c_void_p(np_.data_ptr()), None,
+                                              self.batch._stream()))
+        self._keep_ret = (np_,)
+
+    def minibatch(self, index, advantages=None):
+        """index[i] = t * N + e with t in 0 .. T - 1 (the flat indices of the reference's [:-1] views) ->
+        (obs, actions, returns, masks, old_log_probs, adv, values): obs as gather() returns it, the others [B, 1].  One gather and
+        one kernel for the six small columns.  advantages [T, N]: the caller's (normalised) ones; None: the stored advantages.
+        An index list on the host is checked first (check_rollout_column_indices: ValueError, nothing launched); a LongTensor on
+        the device is read in place, a row out of range comes back as zeros and is counted (rejected())."""
+        torch, b = self.torch, self.batch
+        if torch.is_tensor(index) and index.device == b.device:
+            idx = index.reshape(-1).to(torch.int64).contiguous()
+        else:
+            host = index.cpu().numpy() if torch.is_tensor(index) else index
+            idx = torch.from_numpy(check_rollout_column_indices(host, self.num_steps, self.num_envs)).to(b.device)
+        adv = None if advantages is None else self._column("minibatch: advantages", advantages, self.num_steps * self.num_envs, (torch.float32,))
+        obs = self.gather(idx)
+        B = idx.numel()
+        cols = torch.empty((5, B, 1), dtype=torch.float32, device=b.device)
+        act = torch.empty((B, 1), dtype=torch.int64, device=b.device)
+        _lib.check(self.L.mwb_rollout_gather_cols(b.h, ctypes.c_void_p(idx.data_ptr()), int(B), None if adv is None else ctypes.c_void_p(adv.data_ptr()),
+                                                  ctypes.c_void_p(cols.data_ptr()), ctypes.c_void_p(act.data_ptr()), b._stream()))
+        self._keep_adv = adv
+        return obs, act, cols[0], cols[4], cols[2], cols[3], cols[1]
+
+    def feed_forward_generator(self, advantages, num_mini_batch, generator=None):
+        """RolloutStorage.feed_forward_generator (storage.py:110-131): yields (obs, None, actions, returns, masks, old_log_probs,
+        adv_targ) - None where the reference has the recurrent hidden states - over a random permutation of the T * N transitions
+        drawn on the device (generator: a torch.Generator of the batch's device), cut into batches of T * N // num_mini_batch as
+        BatchSampler(drop_last=False) cuts them: the last one may be shorter."""
+        torch = self.torch
+        batch_size = self.num_steps * self.num_envs
+        assert batch_size >= num_mini_batch, (
+            "PPO requires the number of processes ({}) * number of steps ({}) = {} to be greater than or equal to the number of "
+            "PPO mini batches ({}).".format(self.num_envs, self.num_steps, batch_size, num_mini_batch))
+        mini_batch_size = batch_size // num_mini_batch
+        perm = torch.randperm(batch_size, device=self.batch.device, generator=generator)
+        for first in range(0, batch_size, mini_batch_size):
+            obs, act, ret, mask, logp, adv, _ = self.minibatch(perm[first:first + mini_batch_size], advantages)
+            yield obs, None, act, ret, mask, logp, adv
 
     def rejected(self):
         """rows of gathers whose index was out of range since the last call (synchronous)"""
@@ -726,12 +849,14 @@ class BatchedMiniWorld:
         return self.stack
 
     # --------------------------------------------------------------------------- rollout storage
-    def rollout_enable(self, num_steps, nstack=4, grey=False):
+    def rollout_enable(self, num_steps, nstack=4, grey=False, learner=False):
         """The observation half of the trainer's RolloutStorage on the device (mwb_rollout_enable): a ring of num_steps + nstack
         single frames - uint8 RGB, or with grey=True (needs greyscale=True at construction) the float32 grey frames - instead of
         num_steps + 1 stacked float32 observations, and the rewards / masks / features rows.  Needs layout='CWH'.  Returns the
-        Rollout (also self.rollout): push() after every reset() / step(), gather(idx) for the minibatches."""
-        self.rollout = Rollout(self, num_steps, nstack, grey)
+        Rollout (also self.rollout): push() after every reset() / step(), gather(idx) for the minibatches.  learner=True: the
+        learner half as well (Rollout.learner_enable): actions, log-probs, value predictions, `taken`, the returns / GAE scan and
+        the minibatch tuples."""
+        self.rollout = Rollout(self, num_steps, nstack, grey, learner=learner)
         return self.rollout
 
     def frame_reuse_stats(self):

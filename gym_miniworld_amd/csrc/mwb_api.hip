@@ -16,6 +16,7 @@
 #include "mwb_internal.h"
 #include "mwb_lds_layout.h"
 #include "mwb_rollout_map.h"
+#include "mwb_returns_scan.h"
 #include "mwb_task_table.h"
 #include "mwb_texture_host.h"
 
@@ -107,6 +108,10 @@ struct mwb_handle {
     bool rollout_on = false;
     MwbRollout rollout = {};
     size_t rollout_ring_bytes = 0;
+    // ---- its learner half (mwb_rollout_learner_enable)
+    bool learner_on = false;
+    MwbLearner learner = {};
+    bool last_pass_repeat = false;      // the last pass on the handle was an mwb_step_repeat: a push records its `taken` buffer
 };
 #define MWB_COPY_TABLE_DESCS 64
 static unsigned long long g_next_serial = 1;
@@ -367,6 +372,11 @@ static void rollout_free(MwbRollout &r) {
     for (void *p : ps) if (p) hipFree(p);
     r = MwbRollout{};
 }
+static void learner_free(MwbLearner &l) {
+    void *ps[] = {l.action, l.log_prob, l.value, l.taken, l.ret, l.adv, l.psi_ret};
+    for (void *p : ps) if (p) hipFree(p);
+    l = MwbLearner{};
+}
 
 extern "C" int mwb_destroy(mwb_handle *h) {
     if (!h) return MWB_OK;
@@ -377,6 +387,7 @@ extern "C" int mwb_destroy(mwb_handle *h) {
     if (h->mesh_data_dev) hipFree(h->mesh_data_dev);
     if (h->copy_pairs) hipFree(h->copy_pairs);
     rollout_free(h->rollout);
+    learner_free(h->learner);
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
@@ -605,6 +616,7 @@ extern "C" int mwb_reset(mwb_handle *h, const uint8_t *mask_dev, void *stream) {
     USE_DEVICE(h->cfg.device);
     int rc = ensure_ready(h); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    h->last_pass_repeat = false;
     h->dev.step_pass = 0; h->dev.reuse_pass = 0;   // every frame is rendered (and the last-frame cache refreshed)
     rc = timing_begin(h, s); if (rc) return rc;
     rc = stack_advance(h, mask_dev == nullptr, s); if (rc) return rc;   // a full reset restarts the window; a partial one is a step for the others
@@ -653,6 +665,7 @@ static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *s
     int rc = ensure_ready(h); if (rc) return rc;
     if (!actions_dev) return set_err(MWB_EINVAL, "mwb_step: null actions");
     hipStream_t s = (hipStream_t)stream;
+    h->last_pass_repeat = repeat > 0;
     h->dev.reuse_pass = 1;   // an env the step kernel finds unchanged gets its last frame copied instead of rendered (d.frame_same)
     h->dev.step_pass = 1;   // the frames of this pass are the step's own (entity tasks: what a task rule removed is still drawn)
     rc = timing_begin(h, s); if (rc) return rc;
@@ -940,6 +953,10 @@ extern "C" int mwb_rollout_push(mwb_handle *h, int after_reset, const uint8_t *f
     HIP_TRY(hipMemcpyAsync(r.ring + (size_t)mwb_rollout_slot(r.base, t, 0, r.R) * slab, frames, slab, hipMemcpyDeviceToDevice, s));
     mwb_launch_rollout_push(r, t, after_reset != 0, fresh_dev, d.done, d.reward, d.feature, s);
     if (int rc = check_launch("rollout_push_kernel")) return rc;
+    if (h->learner_on && !after_reset) {   // taken[t - 1]: the repeat's count, or 1 for a plain step and for a pass that is not a step
+        mwb_launch_rollout_taken(r, h->learner, t, (h->last_pass_repeat && !fresh_dev) ? h->rep_taken : nullptr, s);
+        if (int rc = check_launch("rollout_taken_kernel")) return rc;
+    }
     r.cursor = t;
     return MWB_OK;
 }
@@ -996,6 +1013,94 @@ extern "C" int mwb_rollout_rejected(mwb_handle *h, unsigned long long *rows) {
     HIP_TRY(hipMemset(h->rollout.rejected, 0, sizeof(*rows)));
     HIP_TRY(hipDeviceSynchronize());
     return MWB_OK;
+}
+
+// ------------------------------------------------------------------- rollout storage: the learner half
+// the small columns and the returns scan; the arithmetic is mwb_returns_scan.h, the kernels mwb_rollout_learner.hip
+static_assert(MWB_RETURNS_MAX_K == MWB_MAX_REPEAT, "the discount tables have one row per possible `taken`");
+static_assert(MWB_SCAN_DISCOUNTED == MWB_RETURNS_DISCOUNTED && MWB_SCAN_GAE == MWB_RETURNS_GAE && MWB_SCAN_PSI == MWB_RETURNS_PSI, "mode numbers");
+
+extern "C" int mwb_rollout_learner_enable(mwb_handle *h) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_learner_enable: null handle");
+    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_learner_enable: call mwb_rollout_enable first");
+    if (h->learner_on) return set_err(MWB_ESTATE, "mwb_rollout_learner_enable: already enabled");
+    USE_DEVICE(h->cfg.device);
+    const size_t N = (size_t)h->rollout.N, T = (size_t)h->rollout.T, T1 = T + 1;
+    MwbLearner l = {};
+    int rc = MWB_OK;
+    auto get = [&](auto *&p, size_t bytes) {
+        if (rc != MWB_OK) return;
+        void *q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) { rc = set_err(MWB_ENOMEM, std::string("mwb_rollout_learner_enable: hipMalloc failed: ") + hipGetErrorString(e)); return; }
+        p = static_cast<std::remove_reference_t<decltype(p)>>(q);
+        if ((e = hipMemset(q, 0, bytes)) != hipSuccess) rc = set_err(MWB_EHIP, std::string("mwb_rollout_learner_enable: hipMemset failed: ") + hipGetErrorString(e));
+    };
+    get(l.action, T * N * sizeof(int64_t)); get(l.log_prob, T * N * sizeof(float)); get(l.value, T1 * N * sizeof(float));
+    get(l.taken, T * N * sizeof(int32_t)); get(l.ret, T1 * N * sizeof(float)); get(l.adv, T * N * sizeof(float));
+    get(l.psi_ret, T1 * N * 2 * sizeof(float));
+    // a transition is one sub-step until a push says otherwise
+    if (rc == MWB_OK && hipMemsetD32((hipDeviceptr_t)l.taken, 1, T * N) != hipSuccess) rc = set_err(MWB_EHIP, "mwb_rollout_learner_enable: hipMemsetD32 failed");
+    if (rc == MWB_OK && hipDeviceSynchronize() != hipSuccess) rc = set_err(MWB_EHIP, "mwb_rollout_learner_enable: hipDeviceSynchronize failed");
+    if (rc != MWB_OK) { learner_free(l); return rc; }   // the handle is as it was
+    h->learner = l; h->learner_on = true;
+    return MWB_OK;
+}
+
+extern "C" int mwb_rollout_learner_info(mwb_handle *h, struct mwb_rollout_learner_info *out) {
+    if (!h || !out) return set_err(MWB_EINVAL, "mwb_rollout_learner_info: null argument");
+    if (!h->learner_on) return set_err(MWB_ESTATE, "mwb_rollout_learner_info: call mwb_rollout_learner_enable first");
+    const MwbLearner &l = h->learner;
+    const size_t N = (size_t)h->rollout.N, T = (size_t)h->rollout.T, T1 = T + 1;
+    memset(out, 0, sizeof(*out));
+    out->action = l.action; out->log_prob = l.log_prob; out->value = l.value; out->taken = l.taken; out->ret = l.ret; out->adv = l.adv;
+    out->psi_ret = l.psi_ret;
+    out->action_bytes = T * N * sizeof(int64_t); out->log_prob_bytes = T * N * sizeof(float); out->value_bytes = T1 * N * sizeof(float);
+    out->taken_bytes = T * N * sizeof(int32_t); out->ret_bytes = T1 * N * sizeof(float); out->adv_bytes = T * N * sizeof(float);
+    out->psi_ret_bytes = T1 * N * 2 * sizeof(float);
+    return MWB_OK;
+}
+
+extern "C" int mwb_rollout_insert(mwb_handle *h, const int64_t *action_dev, const int32_t *action_i32_dev, const float *log_prob_dev,
+                                  const float *value_dev, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_insert: null handle");
+    if (!h->learner_on) return set_err(MWB_ESTATE, "mwb_rollout_insert: call mwb_rollout_learner_enable first");
+    if (action_dev && action_i32_dev) return set_err(MWB_EINVAL, "mwb_rollout_insert: at most one of action / action_i32 may be given");
+    const MwbRollout &r = h->rollout;
+    if (r.cursor < 1) return set_err(MWB_ESTATE, "mwb_rollout_insert: no transition has been pushed in this window yet");
+    if (!action_dev && !action_i32_dev && !log_prob_dev && !value_dev) return MWB_OK;
+    USE_DEVICE(h->cfg.device);
+    mwb_launch_rollout_insert(r, h->learner, r.cursor - 1, action_dev, action_i32_dev, log_prob_dev, value_dev, (hipStream_t)stream);
+    return check_launch("rollout_insert_kernel");
+}
+
+extern "C" int mwb_rollout_returns(mwb_handle *h, int mode, double gamma, double tau, const float *next_value_dev, const float *next_psi_dev,
+                                   const float *reward_override_dev, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_returns: null handle");
+    if (!h->learner_on) return set_err(MWB_ESTATE, "mwb_rollout_returns: call mwb_rollout_learner_enable first");
+    if (mode != MWB_RETURNS_DISCOUNTED && mode != MWB_RETURNS_GAE && mode != MWB_RETURNS_PSI) return set_err(MWB_EINVAL, "mwb_rollout_returns: unknown mode");
+    const MwbRollout &r = h->rollout;
+    if (r.cursor != r.T) return set_err(MWB_ESTATE, "mwb_rollout_returns: the rollout does not hold num_steps steps yet");
+    const float *next = mode == MWB_RETURNS_PSI ? next_psi_dev : next_value_dev;
+    if (!next) return set_err(MWB_EINVAL, mode == MWB_RETURNS_PSI ? "mwb_rollout_returns: MWB_RETURNS_PSI needs next_psi" : "mwb_rollout_returns: next_value is null");
+    USE_DEVICE(h->cfg.device);
+    MwbReturnsTables tab;
+    mwb_returns_tables(gamma, tau, &tab);
+    mwb_launch_rollout_returns(r, h->learner, mode, tab, next, reward_override_dev ? reward_override_dev : r.reward, (hipStream_t)stream);
+    return check_launch("rollout_returns_kernel");
+}
+
+extern "C" int mwb_rollout_gather_cols(mwb_handle *h, const int64_t *index_dev, int count, const float *adv_src_dev, float *out_f32_dev,
+                                       int64_t *out_action_dev, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_gather_cols: null handle");
+    if (!h->learner_on) return set_err(MWB_ESTATE, "mwb_rollout_gather_cols: call mwb_rollout_learner_enable first");
+    if (count < 0) return set_err(MWB_EINVAL, "mwb_rollout_gather_cols: count < 0");
+    if (count == 0) return MWB_OK;
+    if (!index_dev || !out_f32_dev || !out_action_dev) return set_err(MWB_EINVAL, "mwb_rollout_gather_cols: null argument");
+    USE_DEVICE(h->cfg.device);
+    mwb_launch_rollout_gather_cols(h->rollout, h->learner, index_dev, count, adv_src_dev ? adv_src_dev : h->learner.adv, out_f32_dev, out_action_dev,
+                                   (hipStream_t)stream);
+    return check_launch("rollout_gather_cols_kernel");
 }
 
 // ------------------------------------------------------------------------------ copying environments

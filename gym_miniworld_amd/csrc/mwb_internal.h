@@ -370,6 +370,24 @@ void mwb_launch_rollout_push(const MwbRollout &r, int t, int after_reset, const 
 void mwb_launch_rollout_after_update(const MwbRollout &r, hipStream_t s);
 void mwb_launch_rollout_gather(const MwbRollout &r, const int64_t *index, int count, void *out, int out_float, hipStream_t s);
 
+// ---- the rollout's learner half (mwb_rollout_learner_enable): the small columns of RolloutStorage and what is computed from them
+struct MwbLearner {
+    int64_t *action;                 // [T][N]
+    float *log_prob, *value;         // [T][N], [T + 1][N]
+    int32_t *taken;                  // [T][N] sub-steps of the transition t -> t + 1
+    float *ret, *adv, *psi_ret;      // [T + 1][N], [T][N], [T + 1][N][2]
+};
+struct MwbReturnsTables;   // mwb_returns_scan.h
+// launch wrappers implemented in mwb_rollout_learner.hip.  taken: the row of the push to time t (> 0), `taken` = NULL writes 1;
+// returns: mode = MWB_RETURNS_*, next = next_value or next_psi, reward = the rows to use; gather_cols: count > 0
+void mwb_launch_rollout_taken(const MwbRollout &r, const MwbLearner &l, int t, const int32_t *taken, hipStream_t s);
+void mwb_launch_rollout_insert(const MwbRollout &r, const MwbLearner &l, int row, const int64_t *action, const int32_t *action_i32,
+                               const float *log_prob, const float *value, hipStream_t s);
+void mwb_launch_rollout_returns(const MwbRollout &r, const MwbLearner &l, int mode, const MwbReturnsTables &tab, const float *next,
+                                const float *reward, hipStream_t s);
+void mwb_launch_rollout_gather_cols(const MwbRollout &r, const MwbLearner &l, const int64_t *index, int count, const float *adv_src,
+                                    float *out_f32, int64_t *out_action, hipStream_t s);
+
 // launch wrappers implemented in mwb_kernels.hip
 void mwb_launch_step(const MwbDev &d, const int32_t *actions, const uint8_t *skip_mask, hipStream_t s);   // entity tasks: step_ents_kernel
 void mwb_launch_clear_list(const MwbDev &d, hipStream_t s);

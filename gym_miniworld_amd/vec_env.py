@@ -134,6 +134,10 @@ class MiniWorldVecEnv(VecEnv):
                        and the grey frames with greyscale=True; envs.rollout.gather(idx) rebuilds the stacked observations of a
                        minibatch, envs.rollout.after_update() replaces rollouts.after_update().  A step beyond T raises the
                        library's MWB_ESTATE message before anything is stepped.  Not with graph=True (host-side cursor)
+    rollout_learner=True -> with rollout_steps: the rollout's learner half too (Rollout.learner_enable).  Every step records the
+                       actions it was given (int32 or int64, as handed over) and, with frame_skip=k, the sub-steps it took; the
+                       trainer calls envs.rollout.insert(value, log_prob) after the step, then compute_returns(...) and
+                       feed_forward_generator(...): no second storage object
     feature_info    -> every info dict carries "feature" (length-2 zeros) as the fork's PPO loop
                        requires (pytorch-a2c-ppo-acktr/main.py:614-619)
     graph=True      -> after two eager steps the whole step (mwb_step's kernels on both streams, the frame-stack /
@@ -148,7 +152,7 @@ class MiniWorldVecEnv(VecEnv):
 
     def __init__(self, env_id, num_envs, seed=1, device=0, domain_rand=False, transpose=True, to_float=True,
                  frame_stack=0, torch_api=True, feature_info=False, first_env_index=0, graph=False, greyscale=False, frame_skip=1,
-                 rollout_steps=0, **kwargs):
+                 rollout_steps=0, rollout_learner=False, **kwargs):
         import torch
         from .batch import BatchedMiniWorld
         from . import _lib
@@ -157,6 +161,8 @@ class MiniWorldVecEnv(VecEnv):
         if rollout_steps and graph:
             raise ValueError("rollout_steps cannot be combined with graph=True: the rollout's cursor and ring position live on the "
                              "host, a replayed graph would freeze them")
+        if rollout_learner and not rollout_steps:
+            raise ValueError("rollout_learner needs rollout_steps=T: the learner half belongs to a rollout")
         if rollout_steps and not transpose:
             raise ValueError("rollout_steps needs transpose=True: the rollout stores channel-first frames")
         from .batch import check_repeat_args
@@ -184,7 +190,8 @@ class MiniWorldVecEnv(VecEnv):
                 # observations rendered in tiles (frames too large for one workgroup's LDS, MWB_TILE): the sliding window, one pass
                 self.stackedobs = b.stack_enable(self.nstack, "float32" if to_float else "uint8", sliding=not graph, fused=False)
         # the trainer's RolloutStorage on the device: pushed by reset() and by the device part of every step
-        self.rollout = b.rollout_enable(int(rollout_steps), nstack=self.nstack or 1, grey=self.greyscale) if rollout_steps else None
+        self.rollout = b.rollout_enable(int(rollout_steps), nstack=self.nstack or 1, grey=self.greyscale,
+                                        learner=bool(rollout_learner)) if rollout_steps else None
         VecEnv.__init__(self, num_envs, Box(0, 255, shape, np.float32 if to_float else np.uint8), Discrete(b.n_actions))
         self.device = b.device
         self.feature_info = feature_info
@@ -246,6 +253,8 @@ class MiniWorldVecEnv(VecEnv):
             b.step(a, skip_mask=skip)
         if ro is not None:
             ro.push()
+            if ro.learner:
+                ro.insert(action=a)   # the actions of the transition just pushed; value / log_prob are the trainer's to insert
         obs = self._obs_out(done=b.done)
         self._h_pack.copy_(b.pack[:self._pack_need], non_blocking=True)   # one copy: the small outputs share an allocation
         if self._h_taken is not None:

@@ -455,6 +455,63 @@ struct mwb_rollout_info {
 int mwb_rollout_info(mwb_handle *h, struct mwb_rollout_info *out);   /* MWB_ESTATE before mwb_rollout_enable */
 int mwb_rollout_rejected(mwb_handle *h, unsigned long long *rows);   /* synchronous; reads and clears */
 
+/* ---- rollout storage, the learner half: small columns, returns / GAE scan, minibatch columns -------- */
+/* replaces: the rest of RolloutStorage (storage.py:15-18,32-34): actions, action_log_probs, value_preds, returns, psi_returns -
+ * and what no reference array holds: `taken`, the sub-steps every transition took (mwb_step_repeat), by which the scans below
+ * discount.  Opt-in: a handle that never calls this launches exactly what it launched before.  Call after mwb_rollout_enable;
+ * MWB_ESTATE before it, or when already enabled.  Allocates, with T = num_steps (mwb_destroy frees them):
+ *   action i64 [T][N], log_prob f32 [T][N], value f32 [T+1][N], taken i32 [T][N], ret f32 [T+1][N], adv f32 [T][N],
+ *   psi_ret f32 [T+1][N][2] - all zeros, except taken, which starts as 1.
+ * From then on mwb_rollout_push(after_reset == 0) to time t also writes taken[t-1][e], in a small launch of its own: the taken
+ * buffer of the mwb_step_repeat if that was the last pass on the handle (0 for an env its skip mask named), 1 after mwb_step /
+ * mwb_step_i64, and 1 when fresh_dev is given (a pass that is not a step).  The handle remembers the kind of the last pass on
+ * the host. */
+int mwb_rollout_learner_enable(mwb_handle *h);
+/* replaces: the columns of RolloutStorage.insert (storage.py:57-61) - actions[step], action_log_probs[step], value_preds[step]
+ * of the transition that led to the last push: row cursor - 1 of action, log_prob and value.  Device arrays of num_envs
+ * entries; every pointer may be NULL (that column keeps what it holds; storage.py:58-61 skip None the same way), at most one of
+ * action_dev (i64) and action_i32_dev (widened) may be given: MWB_EINVAL otherwise.  MWB_ESTATE when the cursor is less than 1
+ * (nothing pushed since the reset push or since after_update).  Nothing changes on an error. */
+int mwb_rollout_insert(mwb_handle *h, const int64_t *action_dev, const int32_t *action_i32_dev, const float *log_prob_dev,
+                       const float *value_dev, void *stream);
+/* replaces: RolloutStorage.compute_returns (storage.py:82-99; MWB_RETURNS_GAE = use_gae, MWB_RETURNS_DISCOUNTED otherwise) and
+ * compute_psi_returns (storage.py:101-105; MWB_RETURNS_PSI), the num_steps-long Python loops over tiny tensors: one kernel, one
+ * lane per env, sequential over t.  The results are bit-equal to torch's eager float32 arithmetic in the reference's operation
+ * order (csrc/mwb_returns_scan.h states every operation), with one extension: the transition t -> t+1 is discounted by
+ * G[k] = (float)(gamma^k) - and L[k] = (float)((gamma * tau)^k) for the GAE trace - with k = taken[t][e] clamped to
+ * 0 .. MWB_MAX_REPEAT, the powers formed in float64 by repeated multiplication.  With taken == 1 everywhere that is the reference.
+ *   GAE:        value[T] = ret[T] = next_value; gae = 0; for t = T-1 .. 0:
+ *               delta = reward[t] + G[k] * value[t+1] * mask[t+1] - value[t]; gae = delta + L[k] * mask[t+1] * gae;
+ *               ret[t] = gae + value[t]
+ *   DISCOUNTED: value[T] = ret[T] = next_value; ret[t] = ret[t+1] * G[k] * mask[t+1] + reward[t]
+ *   PSI:        psi_ret[T] = next_psi; psi_ret[t] = psi_ret[t+1] * G[k] * mask[t+1] + feature[t], per component
+ * GAE and DISCOUNTED also write adv[t] = ret[t] - value[t] (ppo.py:33; normalising them stays with the caller).
+ * next_value_dev: f32 [N] (GAE, DISCOUNTED); next_psi_dev: f32 [N][2] (PSI); the one the mode does not use is ignored.
+ * reward_override_dev: f32 [T][N] or NULL, read instead of the stored rewards (the sf=True branch's estimated_rewards,
+ * storage.py:92-95); ignored by PSI.  tau is used by GAE only.  MWB_ESTATE unless the cursor is at num_steps; MWB_EINVAL for an
+ * unknown mode or when the mode's `next` array is NULL.  Nothing changes on an error. */
+#define MWB_RETURNS_DISCOUNTED 0
+#define MWB_RETURNS_GAE 1
+#define MWB_RETURNS_PSI 2
+int mwb_rollout_returns(mwb_handle *h, int mode, double gamma, double tau, const float *next_value_dev, const float *next_psi_dev,
+                        const float *reward_override_dev, void *stream);
+/* replaces: the six small `tensor.view(-1, 1)[indices]` of a minibatch (storage.py:124-128, ppo.py:41-43): one kernel.
+ * index_dev: device i64[count], the flat indices of the [:-1] views: idx = t * N + e with t in 0 .. T-1.  out_f32_dev: f32
+ * [5][count] = return, value prediction, old log-prob, advantage, mask of the rows; out_action_dev: i64 [count].  adv_src_dev:
+ * f32 [T*N], the caller's (normalised, ppo.py:34) advantages, or NULL for the stored adv.  A row whose index lies outside
+ * [0, T*N) is written as zeros and counted in mwb_rollout_rejected; no address is formed from it.  count == 0 is a no-op. */
+int mwb_rollout_gather_cols(mwb_handle *h, const int64_t *index_dev, int count, const float *adv_src_dev, float *out_f32_dev,
+                            int64_t *out_action_dev, void *stream);
+/* the learner half's device arrays (fixed for the handle's lifetime); MWB_ESTATE before mwb_rollout_learner_enable */
+struct mwb_rollout_learner_info {
+    int64_t *action;                  /* i64 [T][N] */
+    float *log_prob, *value;          /* f32 [T][N], [T+1][N] */
+    int32_t *taken;                   /* i32 [T][N] */
+    float *ret, *adv, *psi_ret;       /* f32 [T+1][N], [T][N], [T+1][N][2] */
+    size_t action_bytes, log_prob_bytes, value_bytes, taken_bytes, ret_bytes, adv_bytes, psi_ret_bytes;
+};
+int mwb_rollout_learner_info(mwb_handle *h, struct mwb_rollout_learner_info *out);
+
 /* World generation cannot fail for the four tasks with sane arguments; if it ever does (a portal outside
  * its wall, more than one portal on an edge, a placement that finds no free spot in 100000 draws - the
  * reference would assert or spin) the kernel flags it. Synchronous: returns MWB_ESTATE if any env of the
