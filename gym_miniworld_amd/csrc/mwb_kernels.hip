@@ -121,6 +121,13 @@ __device__ __forceinline__ bool seg_hit(SegPtr sg, double px, double pz, double 
     return dist < radius;
 }
 
+// np.linalg.norm of ONE vector - the distance between two entities (miniworld.py:955, 970; simtorealpush.py:100, 119, 131) - is
+// sqrt(x.dot(x)), and that dot product is BLAS's ddot, not NumPy's own sum: the x86-64 kernels of OpenBLAS (every target since
+// Haswell) run a vector of three through their scalar tail `dot += y[i] * x[i]`, compiled to fused multiply-adds.  The golden
+// files tests/golden/stepedge_*.npz carry that rounding - it is an ulp off (x x + y y) + z z for a fifth of all vectors - and
+// at a threshold it decides.  (The norm over axis 1 of intersect_circle_segs, seg_hit above, is NumPy's plain sum.)
+__device__ __forceinline__ double norm1d(double x, double y, double z) { return sqrt(fma(z, z, fma(y, y, x * x))); }
+
 // circle vs ALL of env e's wall segments by one lane (the carry / pickup tests, the entity tasks, mwb_intersect): group by group,
 // the group's box first (d.seg_box, mwb_seg_groups.h).  A group whose box grown by radius + 1e-9 excludes the point has no segment
 // within the radius - seg_hit would say no to each - so its segments are not loaded.
@@ -246,7 +253,7 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
                     for (int cc = 0; cc < 4; cc++) wq[i][cc] = d.segs[(size_t)((i < ns ? i : 0) * 4 + cc) * d.N + e];
                 for (int b = 0; b < 2; b++) {
                     const double vx = bx[b] - npx, vz = bz[b] - npz;
-                    const double dist = sqrt((vx * vx + 0.0) + vz * vz);
+                    const double dist = norm1d(vx, 0.0, vz);
                     if (dist < arad + brad[b]) {
                         const double qx = bx[b] + vx, qz = bz[b] + vz;
                         bool hit = false;
@@ -255,8 +262,8 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
                         if (!hit) {   // entities in list order: box 0, box 1, agent (itself skipped)
                             const int o = 1 - b;
                             double ddx = bx[o] - qx, ddz = bz[o] - qz;
-                            hit = sqrt(ddx * ddx + 0.0 + ddz * ddz) < brad[b] + brad[o];
-                            if (!hit) { ddx = ax - qx; ddz = az - qz; hit = sqrt(ddx * ddx + 0.0 + ddz * ddz) < brad[b] + arad; }
+                            hit = norm1d(ddx, 0.0, ddz) < brad[b] + brad[o];
+                            if (!hit) { ddx = ax - qx; ddz = az - qz; hit = norm1d(ddx, 0.0, ddz) < brad[b] + arad; }
                         }
                         if (!hit) {
                             bx[b] = qx; bz[b] = qz;
@@ -378,12 +385,12 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
 #pragma unroll
         for (int b = NBX - 1; b >= 0; b--) {   // descending, so that the lowest index wins
             const double ddx = bx[b] - px, ddz = bz[b] - pz;
-            const bool h = b < NB && b != self_idx && sqrt(ddx * ddx + 0.0 + ddz * ddz) < radius + brad[b];
+            const bool h = b < NB && b != self_idx && norm1d(ddx, 0.0, ddz) < radius + brad[b];
             res = h ? 2 + b : res;
         }
         if (!res && self_idx != NB) {   // the agent is the last entity of the list
             const double ddx = ax - px, ddz = az - pz;
-            if (sqrt(ddx * ddx + 0.0 + ddz * ddz) < radius + arad) res = 2 + NB;
+            if (norm1d(ddx, 0.0, ddz) < radius + arad) res = 2 + NB;
         }
         return res;
     };
@@ -462,7 +469,7 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
 #pragma unroll
         for (int b = 0; b < NBX; b++) {   // np.linalg.norm(ent0.pos - ent1.pos): a carried box is off the floor
             double ddx = bx[b] - ax, ddy = by[b] - 0.0, ddz = bz[b] - az;
-            double dist = sqrt((ddx * ddx + ddy * ddy) + ddz * ddz);
+            double dist = norm1d(ddx, ddy, ddz);
             near[b] = b < NB && dist < brad[b] + arad + 1.1 * max_forward_step;
         }
         const double rw = 1.0 - 0.2 * ((double)sc / d.max_episode_steps);   // _reward, miniworld.py:1012
@@ -479,11 +486,11 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
             d.goal_pos[e * 3] = g ? bx[I1] : bx[0]; d.goal_pos[e * 3 + 1] = 0.0; d.goal_pos[e * 3 + 2] = g ? bz[I1] : bz[0];   // info['goal_pos']
         } else if (NBX == 2 && d.task == MWB_TASK_SIM2REAL_PUSH) {   // simtorealpush.py:129-133: the boxes are close enough
             const double ddx = bx[0] - bx[I1], ddz = bz[0] - bz[I1];
-            if (sqrt((ddx * ddx + 0.0) + ddz * ddz) < d.goal_dist[e]) { r = 1.0; done = 1; }
+            if (norm1d(ddx, 0.0, ddz) < d.goal_dist[e]) { r = 1.0; done = 1; }
         } else if (NBX == 6 && d.task == MWB_TASK_PUTNEXT) {   // putnext.py:45-53: red (box 4) next to yellow (box 5), nothing carried
             if (carried < 0) {
                 const double ddx = bx[I4] - bx[I5], ddy = by[I4] - by[I5], ddz = bz[I4] - bz[I5];
-                if (sqrt((ddx * ddx + ddy * ddy) + ddz * ddz) < brad[I4] + brad[I5] + 1.1 * max_forward_step) { r += rw; done = 1; }
+                if (norm1d(ddx, ddy, ddz) < brad[I4] + brad[I5] + 1.1 * max_forward_step) { r += rw; done = 1; }
             }
         } else {
             if (near[0]) { r += rw; done = 1; }
@@ -557,7 +564,7 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
             if (slot == MWB_ENT_AGENT) { ox = ax; oz = az; orad = arad; }
             else { const size_t be = (size_t)slot * N + e; ox = d.box_x[be]; oz = d.box_z[be]; orad = d.ent_radius[be]; of32 = MWB_META_RADF32(d.ent_meta[be]) != 0; }
             const double ddx = ox - px, ddz = oz - pz;
-            if (sqrt(ddx * ddx + 0.0 + ddz * ddz) < tagged_add(radius, rf32, orad, of32)) return 2 + (slot == MWB_ENT_AGENT ? E : slot);
+            if (norm1d(ddx, 0.0, ddz) < tagged_add(radius, rf32, orad, of32)) return 2 + (slot == MWB_ENT_AGENT ? E : slot);
         }
         return 0;
     };
@@ -627,7 +634,7 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
     auto near = [&](int slot) {   // MiniWorldEnv.near(ent), miniworld.py:961-971
         const size_t be = (size_t)slot * N + e;
         const double ddx = d.box_x[be] - ax, ddy = d.box_y[be] - 0.0, ddz = d.box_z[be] - az;
-        const double dist = sqrt((ddx * ddx + ddy * ddy) + ddz * ddz);
+        const double dist = norm1d(ddx, ddy, ddz);
         bool f32;
         double thr = tagged_add(d.ent_radius[be], MWB_META_RADF32(d.ent_meta[be]) != 0, arad, false, f32);
         thr = tagged_add(thr, f32, 1.1 * max_fwd, false);
@@ -1108,14 +1115,14 @@ struct WorldGen {
             bool blocked = false;
             for (int k = 0; k < opt.n_others; k++) {
                 double ddx = opt.other_x[k] - px, ddz = opt.other_z[k] - pz;
-                double dist = sqrt(ddx * ddx + 0.0 + ddz * ddz);
+                double dist = norm1d(ddx, 0.0, ddz);
                 const double orad = opt.other_r[k] >= 0 ? opt.other_r[k] : ((k == 1 && opt.other_radius2 >= 0) ? opt.other_radius2 : opt.other_radius);
                 if (dist < radius + orad) blocked = true;
             }
             if (opt.lds_ents)
                 for (int k = 0; k < n_placed; k++) {
                     double ddx = ent_x[k] - px, ddz = ent_z[k] - pz;
-                    double dist = sqrt(ddx * ddx + 0.0 + ddz * ddz);
+                    double dist = norm1d(ddx, 0.0, ddz);
                     if (dist < tagged_add(radius, opt.self_f32, ent_r[k], ent_f32[k] != 0)) blocked = true;
                 }
             if (blocked) continue;
@@ -1224,7 +1231,7 @@ __global__ void __launch_bounds__(WAVE) reset_kernel(MwbDev d) {
                 o.n_others = 1; o.other_x[0] = box_x; o.other_z[0] = box_z; o.other_radius = brad;
                 w.place_entity_ex(brad2, o, box2_x, box2_z, box2_dir);
                 const double ddx = box_x - box2_x, ddz = box_z - box2_z;
-                if (sqrt((ddx * ddx + 0.0) + ddz * ddz) > goal_dist) break;
+                if (norm1d(ddx, 0.0, ddz) > goal_dist) break;
                 if (attempt == 99999) w.fail = true;
             }
         } else {
@@ -4168,7 +4175,7 @@ __global__ void intersect_kernel(MwbDev d, int e, int ent, double x, double z, d
             if (slot == MWB_ENT_AGENT) { ox = d.agent_x[e]; oz = d.agent_z[e]; orad = d.agent_radius; }
             else { const size_t be = (size_t)slot * d.N + e; ox = d.box_x[be]; oz = d.box_z[be]; orad = d.ent_radius[be]; of32 = MWB_META_RADF32(d.ent_meta[be]) != 0; }
             const double ddx = ox - x, ddz = oz - z;
-            if (sqrt(ddx * ddx + 0.0 + ddz * ddz) < tagged_add(radius, false, orad, of32)) res = 2 + (slot == MWB_ENT_AGENT ? d.n_boxes : slot);
+            if (norm1d(ddx, 0.0, ddz) < tagged_add(radius, false, orad, of32)) res = 2 + (slot == MWB_ENT_AGENT ? d.n_boxes : slot);
         }
         *result = res;
         return;
@@ -4176,11 +4183,11 @@ __global__ void intersect_kernel(MwbDev d, int e, int ent, double x, double z, d
     for (int b = 0; b < d.n_boxes && !res; b++) {
         if (b == ent) continue;
         double ddx = d.box_x[(size_t)b * d.N + e] - x, ddz = d.box_z[(size_t)b * d.N + e] - z;
-        if (sqrt(ddx * ddx + 0.0 + ddz * ddz) < radius + box_radius(d.box_size[(size_t)b * d.N + e])) res = 2 + b;
+        if (norm1d(ddx, 0.0, ddz) < radius + box_radius(d.box_size[(size_t)b * d.N + e])) res = 2 + b;
     }
     if (!res && ent != d.n_boxes) {   // the agent is the last entity of the list
         double ddx = d.agent_x[e] - x, ddz = d.agent_z[e] - z;
-        if (sqrt(ddx * ddx + 0.0 + ddz * ddz) < radius + d.agent_radius) res = 2 + d.n_boxes;
+        if (norm1d(ddx, 0.0, ddz) < radius + d.agent_radius) res = 2 + d.n_boxes;
     }
     *result = res;
 }

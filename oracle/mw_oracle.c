@@ -383,6 +383,11 @@ void mwo_destroy(MwoEnv *e) { if (!e) return; free_rooms(e); free(e); }
 
 void mwo_seed_key(MwoEnv *e, const uint32_t *key, int n) { mt_init_by_array(&e->rng, key, n); }
 
+/* np.linalg.norm of ONE vector - the distance between two entities (miniworld.py:955, 970; simtorealpush.py:100, 119, 131) - is
+ * sqrt(x.dot(x)), and that dot product is BLAS's ddot: the x86-64 kernels of OpenBLAS (every target since Haswell) run a vector of
+ * three through their scalar tail `dot += y[i] * x[i]`, compiled to fused multiply-adds.  tests/golden/stepedge_*.npz carry that
+ * rounding: an ulp off the plain sum for a fifth of all vectors, and at a threshold it decides. */
+static double norm1d(double x, double y, double z) { return sqrt(fma(z, z, fma(y, y, x * x))); }
 static double norm3(const double *v) { /* np.linalg.norm(axis=1): sqrt(add.reduce(v*v)) */
     return sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
 }
@@ -644,7 +649,7 @@ static int intersect_t(MwoEnv *e, const Ent *self, const double *pos, double rad
         const Ent *o = slot == AGENT_SLOT ? &e->agent : &e->boxes[slot];
         if (o == self) continue;
         double d3[3] = {o->pos[0] - p[0], 0 - p[1], o->pos[2] - p[2]}; /* ent2's y is flattened too (miniworld.py:951-952) */
-        double d = sqrt(d3[0] * d3[0] + d3[1] * d3[1] + d3[2] * d3[2]);
+        double d = norm1d(d3[0], d3[1], d3[2]);
         if (d < tagged_add(radius, radius_f32, o->radius, o->rad_f32, NULL)) return 2 + (slot == AGENT_SLOT ? e->n_boxes : slot);
     }
     return 0;
@@ -857,7 +862,7 @@ static void gen_world(MwoEnv *e) {
                 place_entity(e, &e->boxes[0], 0, 0, min_pos, max_pos, min_pos, max_pos);
                 place_entity(e, &e->boxes[1], 0, 0, min_pos, max_pos, min_pos, max_pos);
                 double dx = e->boxes[0].pos[0] - e->boxes[1].pos[0], dy = e->boxes[0].pos[1] - e->boxes[1].pos[1], dz = e->boxes[0].pos[2] - e->boxes[1].pos[2];
-                if (sqrt((dx * dx + dy * dy) + dz * dz) > e->goal_dist) break;
+                if (norm1d(dx, dy, dz) > e->goal_dist) break;
                 e->n_order = 0; /* entities.remove(box1), entities.remove(box2) */
             }
         } else {
@@ -1101,7 +1106,7 @@ void mwo_reset(MwoEnv *e) {
 /* MiniWorldEnv.near, miniworld.py:961-971 */
 static int near_ent(MwoEnv *e, const Ent *b) {
     double d[3] = {b->pos[0] - e->agent.pos[0], b->pos[1] - e->agent.pos[1], b->pos[2] - e->agent.pos[2]};
-    double dist = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    double dist = norm1d(d[0], d[1], d[2]);
     int f32;   /* (ent0.radius + ent1.radius) + 1.1 * max_forward_step, float32 all the way once a float32 radius is in it */
     double thr = tagged_add(b->radius, b->rad_f32, e->agent.radius, 0, &f32);
     thr = tagged_add(thr, f32, 1.1 * e->max_forward_step, 0, NULL);
@@ -1141,7 +1146,7 @@ void mwo_step(MwoEnv *e, int action, double *reward, int *done) {
         for (int b = 0; b < 2; b++) {
             Ent *box = boxes[b];
             double vec[3] = {box->pos[0] - next_pos[0], box->pos[1] - next_pos[1], box->pos[2] - next_pos[2]};
-            double dist = sqrt((vec[0] * vec[0] + vec[1] * vec[1]) + vec[2] * vec[2]);
+            double dist = norm1d(vec[0], vec[1], vec[2]);
             if (dist < e->agent.radius + box->radius) {
                 double nb[3] = {box->pos[0] + vec[0], box->pos[1] + vec[1], box->pos[2] + vec[2]};
                 if (!intersect(e, box, nb, box->radius)) {
@@ -1218,12 +1223,12 @@ void mwo_step(MwoEnv *e, int action, double *reward, int *done) {
         }
     } else if (e->task == MWO_SIM2REAL_PUSH) { /* simtorealpush.py:129-133 */
         double dx = e->boxes[0].pos[0] - e->boxes[1].pos[0], dy = e->boxes[0].pos[1] - e->boxes[1].pos[1], dz = e->boxes[0].pos[2] - e->boxes[1].pos[2];
-        if (sqrt((dx * dx + dy * dy) + dz * dz) < e->goal_dist) { r = 1; d = 1; }
+        if (norm1d(dx, dy, dz) < e->goal_dist) { r = 1; d = 1; }
     } else if (e->task == MWO_PUTNEXT) { /* putnext.py:45-53: red (4) next to yellow (5), nothing carried */
         if (e->carrying < 0) {
             const Ent *a = &e->boxes[4], *b = &e->boxes[5];
             double dd[3] = {a->pos[0] - b->pos[0], a->pos[1] - b->pos[1], a->pos[2] - b->pos[2]};
-            double dist = sqrt(dd[0] * dd[0] + dd[1] * dd[1] + dd[2] * dd[2]);
+            double dist = norm1d(dd[0], dd[1], dd[2]);
             if (dist < a->radius + b->radius + 1.1 * e->max_forward_step) { r += 1.0 - 0.2 * ((double)e->step_count / e->max_episode_steps); d = 1; }
         }
     } else if (e->task == MWO_PICKUPOBJS) { /* pickupobjs.py:56-69: a picked object leaves the list (AFTER the frame was rendered) */

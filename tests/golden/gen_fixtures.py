@@ -39,6 +39,7 @@ TASKS = {
     "Hallway": (Hallway, {}), "OneRoom": (OneRoom, {}), "FourRooms": (FourRooms, {}), "Maze": (Maze, {}),
     "MazeS3": (Maze, {"num_rows": 3, "num_cols": 3}),
     "MazeR2C4": (Maze, {"num_rows": 2, "num_cols": 4, "room_size": 2.5, "max_episode_steps": 200}),
+    "MazeR9C9": (Maze, {"num_rows": 9, "num_cols": 9}),   # 324 segments, 41 groups of eight: past the 256 the step kernel's cull takes in one trip
     "OneRoomS6": (OneRoom, {"size": 6, "max_episode_steps": 100}),
     "Hallway6": (Hallway, {"length": 6}),
     # the T-maze family (envs/tmaze.py); small sub_task_length so that the goal alternation
@@ -66,6 +67,7 @@ PLAN = {
              (65535, 0, "random", 100)],
     "MazeS3": [(0, 0, "greedy", 500), (1, 1, "greedy", 500), (2, 0, "forward", 500), (3, 1, "random", 300)],
     "MazeR2C4": [(0, 0, "greedy", 450), (1, 1, "forward", 450)],
+    "MazeR9C9": [(0, 0, "forward", 300)],
     "OneRoomS6": [(0, 0, "random", 250), (1, 1, "greedy", 150)],
     "Hallway6": [(0, 0, "random", 300), (1, 1, "greedy", 100)],
     "TMaze": [(0, 0, "random", 700), (1, 0, "greedy", 400), (2, 1, "greedy", 400), (3, 1, "forward", 400)],
@@ -594,7 +596,7 @@ def main():
         for dr in (0, 1):
             if task.startswith("Maze") and (dr == 1) != (task == "MazeS3"):
                 continue
-            if task in ("MazeR2C4", "OneRoomS6", "Hallway6"):
+            if task in ("MazeR2C4", "MazeR9C9", "OneRoomS6", "Hallway6"):
                 continue
             if task.startswith("TMaze") and not ((task == "TMaze" and dr == 0) or (task == "TMazeTwoBoxFeatures" and dr == 1)):
                 continue

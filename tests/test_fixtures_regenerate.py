@@ -1,5 +1,5 @@
 """The committed golden vectors are exactly what the generators produce from the unmodified reference: where
-/root/reference exists (the build container) both generators are re-run into a scratch directory and every array /
+/root/reference exists (the build container) the generators are re-run into a scratch directory and every array /
 JSON document is compared with the committed one (round-1 verdict: the files had fallen behind their generator)."""
 import json
 import os
@@ -19,8 +19,10 @@ def test_state_and_glstream_fixtures_round_trip(tmp_path):
     subprocess.check_call([sys.executable, os.path.join(GOLDEN, "gen_fixtures.py"), "--out", out], stdout=subprocess.DEVNULL)
     # the tasks with a general entity list (meshes, frames) have their own generator; meshes.json = digests of the reference's vertex lists
     subprocess.check_call([sys.executable, os.path.join(GOLDEN, "gen_fixtures_ents.py"), "--out", out], stdout=subprocess.DEVNULL)
+    # single steps at the decision edges (stepedge_<task>.npz): start states from tests/step_edges.py, outcomes from the reference
+    subprocess.check_call([sys.executable, os.path.join(GOLDEN, "gen_fixtures_step_edges.py"), "--out", out], stdout=subprocess.DEVNULL)
     names = sorted(f for f in os.listdir(out) if f.endswith((".npz", ".json")))
-    committed = sorted(f for f in os.listdir(GOLDEN) if f.startswith(("state_", "glstream_", "gltop_", "math_kat", "seed_keys", "meshes.json")))
+    committed = sorted(f for f in os.listdir(GOLDEN) if f.startswith(("state_", "stepedge_", "glstream_", "gltop_", "math_kat", "seed_keys", "meshes.json")))
     assert names == committed
     n_arrays = 0
     for f in names:
