@@ -7,14 +7,14 @@ family (TMaze, TMazeLeft / Right, TMazeDynamic, the two-box variants).  See DESI
 from .params import DEFAULT_PARAMS, DomainParams  # noqa: F401
 
 __all__ = ["BatchedMiniWorld", "MiniWorldVecEnv", "MiniWorldEnv", "make", "make_vec_envs", "DEFAULT_PARAMS",
-           "DomainParams", "ENV_SPECS"]
+           "DomainParams", "ENV_SPECS", "Monitor", "evaluate"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the GPU
-    if name in ("BatchedMiniWorld", "ENV_SPECS"):
+    if name in ("BatchedMiniWorld", "ENV_SPECS", "Monitor"):
         from . import batch
         return getattr(batch, name)
-    if name in ("MiniWorldVecEnv", "make_vec_envs", "VecEnv"):
+    if name in ("MiniWorldVecEnv", "make_vec_envs", "VecEnv", "evaluate"):
         from . import vec_env
         return getattr(vec_env, name)
     if name in ("MiniWorldEnv", "make"):

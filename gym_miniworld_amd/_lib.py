@@ -32,6 +32,7 @@ COPY_NO_RENDER = 1   # MWB_COPY_NO_RENDER
 MAX_REPEAT = 64      # MWB_MAX_REPEAT
 ROLLOUT_GREY = 1     # MWB_ROLLOUT_GREY
 RETURNS_DISCOUNTED, RETURNS_GAE, RETURNS_PSI = 0, 1, 2   # MWB_RETURNS_*
+MONITOR_MAX_CAPACITY, MONITOR_MAX_QUOTA = 65536, 64      # csrc/mwb_monitor_map.h
 
 
 class MwbConfig(ctypes.Structure):
@@ -80,6 +81,18 @@ class MwbRolloutLearnerInfo(ctypes.Structure):   # struct mwb_rollout_learner_in
                [(n + "_bytes", ctypes.c_size_t) for n in ("action", "log_prob", "value", "taken", "ret", "adv", "psi_ret")]
 
 
+class MwbMonitorInfo(ctypes.Structure):   # struct mwb_monitor_info
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "run_return", "last_return", "run_len", "run_calls", "last_len", "last_calls", "finished", "partial", "retired", "logged",
+        "log_return", "log_len", "log_calls", "log_env", "tab_return", "tab_len", "counts", "host_pack")] + \
+        [("host_pack_bytes", ctypes.c_size_t)] + [(n, ctypes.c_int32) for n in ("num_envs", "capacity", "quota_max", "pad")]
+
+
+class MwbMonitorCounts(ctypes.Structure):   # struct mwb_monitor_counts, as it lies on the device
+    _fields_ = [("total", ctypes.c_ulonglong), ("dropped", ctypes.c_ulonglong), ("remaining", ctypes.c_uint32), ("quota", ctypes.c_uint32),
+                ("last_base", ctypes.c_uint32), ("last_count", ctypes.c_uint32)]
+
+
 EXPORTS = [
     "mwb_create", "mwb_destroy", "mwb_last_error", "mwb_abi_version", "mwb_set_texture", "mwb_seed", "mwb_reset",
     "mwb_step", "mwb_render", "mwb_get_outputs", "mwb_get_state", "mwb_set_agent", "mwb_intersect",
@@ -92,6 +105,7 @@ EXPORTS = [
     "mwb_rollout_enable", "mwb_rollout_push", "mwb_rollout_gather", "mwb_rollout_after_update", "mwb_rollout_info", "mwb_rollout_rejected",
     "mwb_rollout_learner_enable", "mwb_rollout_learner_info", "mwb_rollout_insert", "mwb_rollout_returns", "mwb_rollout_gather_cols",
     "mwb_bulk_variant",
+    "mwb_monitor_enable", "mwb_monitor_update", "mwb_monitor_clear", "mwb_monitor_quota", "mwb_monitor_info", "mwb_monitor_read",
 ]
 
 _lib = None
@@ -168,6 +182,12 @@ def load():
     L.mwb_rollout_insert.argtypes = [vp, vp, vp, vp, vp, vp]
     L.mwb_rollout_returns.argtypes = [vp, i32, ctypes.c_double, ctypes.c_double, vp, vp, vp, vp]
     L.mwb_rollout_gather_cols.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.mwb_monitor_enable.argtypes = [vp, i32, i32]
+    L.mwb_monitor_update.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.mwb_monitor_clear.argtypes = [vp, vp, i32, vp]
+    L.mwb_monitor_quota.argtypes = [vp, i32, vp]
+    L.mwb_monitor_info.argtypes = [vp, ctypes.POINTER(MwbMonitorInfo)]
+    L.mwb_monitor_read.argtypes = [vp, ctypes.POINTER(MwbMonitorCounts)]
     if hasattr(L, "mwb_bulk_variant"):   # (an older library loaded through MWB_LIB for a kernel A/B has none; build() checks EXPORTS)
         L.mwb_bulk_variant.argtypes = [vp]
     L.mwb_timing_read.argtypes = [vp] +[ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(i32)]

@@ -361,6 +361,120 @@ class Rollout:
         return int(out.value)
 
 
+def monitor_log_slots(total, capacity):
+    """csrc/mwb_monitor_map.h restated once: the ring slots of the live records of the monitor's log, oldest first, for
+    `total` episodes ever appended to a ring of `capacity` records (mwb_monitor_live / mwb_monitor_oldest / mwb_monitor_read_slot)"""
+    total, capacity = int(total), int(capacity)
+    live = min(total, capacity)
+    oldest = 0 if total < capacity else total % capacity
+    return [(oldest + i) % capacity for i in range(live)]
+
+
+class Monitor:
+    """The trainer's record of its own progress on the device (BatchedMiniWorld.monitor_enable; include/miniworld_batch.h at
+    mwb_monitor_enable): per-env running return (float64, summed per episode), length in env steps and in step calls, the episode
+    that ended last in every env, the log of the last `capacity` episodes in the order the reference's loop
+        for idx, eps_done in enumerate(done): if eps_done: episode_rewards.append(...)     (pytorch-a2c-ppo-acktr/main.py:167-169)
+    appends them, and for evaluation a table of every env's first quota_max episodes with a per-env quota.
+        mon.update(skip_mask)      after every step (MiniWorldVecEnv(monitor=K) does it inside the step)
+        mon.log(), mon.stats()     the deque, oldest first, and the statistics main.py:203-214 prints
+        mon.set_quota(q)           from now on env e retires after q episodes: mon.retired is the next step's skip mask
+    run_return, run_len, run_calls, last_return, last_len, last_calls, finished, retired, partial, logged [N] and tab_return,
+    tab_len [quota_max, N] are zero-copy views of the library's arrays."""
+
+    def __init__(self, batch, capacity, quota_max):
+        torch = batch.torch
+        self.batch, self.L, self.torch = batch, batch.L, torch
+        _lib.check(self.L.mwb_monitor_enable(batch.h, int(capacity), int(quota_max)))
+        info = _lib.MwbMonitorInfo()
+        _lib.check(self.L.mwb_monitor_info(batch.h, ctypes.byref(info)))
+        N, C, Q = int(info.num_envs), int(info.capacity), int(info.quota_max)
+        self.num_envs, self.capacity, self.quota_max = N, C, Q
+        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, batch), device=batch.device)  # noqa: E731
+        for name in ("run_return", "last_return"):
+            setattr(self, name, as_t(getattr(info, name), (N,), "<f8"))
+        for name in ("run_len", "run_calls", "last_len", "last_calls", "finished"):
+            setattr(self, name, as_t(getattr(info, name), (N,), "<i4"))
+        for name in ("partial", "retired", "logged"):
+            setattr(self, name, as_t(getattr(info, name), (N,), "|u1"))
+        self._log = (as_t(info.log_return, (C,), "<f8"), as_t(info.log_len, (C,), "<i4"), as_t(info.log_calls, (C,), "<i4"),
+                     as_t(info.log_env, (C,), "<i4"))
+        if Q:
+            self.tab_return, self.tab_len = as_t(info.tab_return, (Q, N), "<f8"), as_t(info.tab_len, (Q, N), "<i4")
+        else:
+            self.tab_return = torch.empty((0, N), dtype=torch.float64, device=batch.device)
+            self.tab_len = torch.empty((0, N), dtype=torch.int32, device=batch.device)
+        # what a host-side consumer wants after every step, in one piece: last_return | last_len | last_calls | counts | logged | retired
+        self.host_pack = as_t(info.host_pack, (int(info.host_pack_bytes),), "|u1")
+        self.host_pack_offsets = {"last_return": 0, "last_len": 8 * N, "last_calls": 12 * N, "counts": 16 * N, "logged": 16 * N + 32,
+                                  "retired": 17 * N + 32}
+        assert int(info.host_pack_bytes) == 18 * N + 32 and ctypes.sizeof(_lib.MwbMonitorCounts) == 32
+        self.quota = 0
+        self._keep = None
+
+    def _arg(self, x, dtype, what):
+        if x is None:
+            return None
+        t = self.torch.as_tensor(x).to(device=self.batch.device, dtype=dtype).reshape(-1).contiguous()
+        if t.numel() != self.num_envs:
+            raise ValueError("monitor %s has %d entries for %d envs" % (what, t.numel(), self.num_envs))
+        return t
+
+    def update(self, skip_mask=None, reward=None, done=None, taken=None):
+        """One pass (mwb_monitor_update) over the batch's own reward64 / done / sub-step counts, or over the arrays given in their
+        place (float64 / uint8 / int32 [N]); skip_mask: the one the step was given."""
+        torch = self.torch
+        if skip_mask is None and reward is None and done is None and taken is None:   # the call of every step: no conversions
+            rc = self.L.mwb_monitor_update(self.batch.h, None, None, None, None, self.batch._stream())
+            if rc:
+                _lib.check(rc)
+            return
+        ts = (self._arg(skip_mask, torch.uint8, "update: skip_mask"), self._arg(reward, torch.float64, "update: reward"),
+              self._arg(done, torch.uint8, "update: done"), self._arg(taken, torch.int32, "update: taken"))
+        ptr = [None if t is None else ctypes.c_void_p(t.data_ptr()) for t in ts]
+        _lib.check(self.L.mwb_monitor_update(self.batch.h, ptr[0], ptr[1], ptr[2], ptr[3], self.batch._stream()))
+        self._keep = ts   # alive until the asynchronous kernels have consumed them
+
+    def clear(self, mask=None, partial=False):
+        """Zero the accumulators of the masked envs (None: all).  partial=False: they start a fresh episode; partial=True: they
+        are in the middle of an episode whose start was not seen, which is dropped, not logged, when it ends."""
+        m = self._arg(mask, self.torch.uint8, "clear: mask")
+        _lib.check(self.L.mwb_monitor_clear(self.batch.h, None if m is None else ctypes.c_void_p(m.data_ptr()), int(bool(partial)),
+                                            self.batch._stream()))
+        self._keep_clear = m
+
+    def set_quota(self, q):
+        """Per-env quota 0 .. quota_max (0: none): zeroes finished / retired, refills the table; the running episodes and the log stay."""
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 0 <= int(q) <= self.quota_max:
+            raise ValueError("monitor quota %r outside 0 .. quota_max = %d" % (q, self.quota_max))
+        _lib.check(self.L.mwb_monitor_quota(self.batch.h, int(q), self.batch._stream()))
+        self.quota = int(q)
+
+    def read(self):
+        """(total, dropped, remaining): episodes ever logged, episodes dropped as partial, envs not retired (synchronous)"""
+        c = _lib.MwbMonitorCounts()
+        _lib.check(self.L.mwb_monitor_read(self.batch.h, ctypes.byref(c)))
+        return int(c.total), int(c.dropped), int(c.remaining)
+
+    def log(self):
+        """The live records of the log, oldest first: (returns f64, lens i32, calls i32, envs i32) device tensors - what
+        list(episode_rewards) holds, with the episode's length and env beside every return.  One read()."""
+        total = self.read()[0]
+        idx = self.torch.as_tensor(monitor_log_slots(total, self.capacity), dtype=self.torch.int64, device=self.batch.device)
+        return tuple(a[idx] for a in self._log)
+
+    def stats(self):
+        """What the trainer prints at a log interval (main.py:203-214) from the log: n, mean, median, min, max, success_rate
+        (returns > 0) and mean_len - computed by torch on the device views; an empty log gives n = 0 and None for the rest."""
+        r, ln, _, _ = self.log()
+        n = int(r.numel())
+        if n == 0:
+            return dict(n=0, mean=None, median=None, min=None, max=None, success_rate=None, mean_len=None)
+        s = r.sort().values
+        return dict(n=n, mean=float(r.sum()) / n, median=float((s[(n - 1) // 2] + s[n // 2]) / 2), min=float(s[0]), max=float(s[-1]),
+                    success_rate=int((r > 0).sum()) / n, mean_len=float(ln.sum()) / n)
+
+
 class _DevView:
     """Exposes a library-owned device buffer through __cuda_array_interface__ (zero-copy)."""
 
@@ -388,6 +502,7 @@ class BatchedMiniWorld:
                           layout=layout, device=device, max_episode_steps=max_episode_steps, params=params, task=task,
                           task_args=task_args, auto_reset=auto_reset, greyscale=greyscale)
         self._stack_args = None
+        self.monitor = None   # monitor_enable()
         self.torch = torch
         self.L = _lib.load()
         if task is None:
@@ -548,6 +663,8 @@ class BatchedMiniWorld:
             mask = mask.to(device=self.device, dtype=self.torch.uint8).contiguous()
             m = ctypes.c_void_p(mask.data_ptr())
         _lib.check(self.L.mwb_reset(self.h, m, self._stream()))
+        if self.monitor is not None:   # the reset envs start a fresh episode
+            self.monitor.clear(mask)
         return self.obs
 
     def step(self, actions, skip_mask=None):
@@ -671,6 +788,14 @@ class BatchedMiniWorld:
         _lib.check(self.L.mwb_copy_envs(self.h, ctypes.c_void_p(d.data_ptr()), src.h, ctypes.c_void_p(s.data_ptr()), int(d.numel()),
                                         0 if render else _lib.COPY_NO_RENDER, self._stream()))
         self._keep_copy = (d, s, src)   # alive until the asynchronous kernels have consumed them
+        if self.monitor is not None and d.numel():
+            # the destinations are now in the middle of their sources' episodes, whose start this monitor did not see: dropped when
+            # they end.  Every index the list names inside the batch is flagged, pairs the device-side validation rejected included
+            # (one episode of such an env goes unlogged); an index outside the batch addresses nothing here
+            ok = (d >= 0) & (d < self.num_envs)
+            hit = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+            hit.index_put_((d.clamp(0, self.num_envs - 1).long(),), ok.to(torch.int32), accumulate=True)
+            self.monitor.clear(hit != 0, partial=True)
         return self.obs
 
     def copy_rejected(self):
@@ -858,6 +983,18 @@ class BatchedMiniWorld:
         the minibatch tuples."""
         self.rollout = Rollout(self, num_steps, nstack, grey, learner=learner)
         return self.rollout
+
+    def monitor_enable(self, capacity=100, quota_max=0):
+        """The episode monitor on the device (mwb_monitor_enable): returns, lengths, the log of the last `capacity` episodes - the
+        trainer's deque(maxlen=100) and its loop over the envs after every step (pytorch-a2c-ppo-acktr/main.py:141,167-169) - and
+        per-env evaluation quotas up to quota_max.  Returns the Monitor (also self.monitor); from now on reset() / reset(mask)
+        clear the reset envs' running episodes and copy_envs() marks its destinations as partial.  Call monitor.update() after
+        every step."""
+        if self.monitor is not None:
+            _lib.check(self.L.mwb_monitor_enable(self.h, int(capacity), int(quota_max)))   # raises the library's MWB_ESTATE message
+        mon = Monitor(self, capacity, quota_max)
+        self.monitor = mon
+        return mon
 
     def frame_reuse_stats(self):
         """(frames reused, frames rendered) by the step passes since the last call (mwb_frame_reuse_stats; synchronous).  A step

@@ -5,6 +5,7 @@
 // caller's stream.  No torch types, no oracle code; fails loudly (negative status + message)
 // rather than falling back to any CPU path.
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -16,6 +17,7 @@
 #include "mwb_internal.h"
 #include "mwb_lds_layout.h"
 #include "mwb_rollout_map.h"
+#include "mwb_monitor_map.h"
 #include "mwb_returns_scan.h"
 #include "mwb_task_table.h"
 #include "mwb_texture_host.h"
@@ -112,6 +114,12 @@ struct mwb_handle {
     bool learner_on = false;
     MwbLearner learner = {};
     bool last_pass_repeat = false;      // the last pass on the handle was an mwb_step_repeat: a push records its `taken` buffer
+    // ---- the episode monitor (mwb_monitor_enable): one allocation of its own, carved into the arrays of `monitor`
+    bool monitor_on = false;
+    MwbMonitor monitor = {};
+    void *monitor_mem = nullptr;
+    void *monitor_pack = nullptr;       // last_return | last_len | last_calls | counts | logged | retired, contiguous
+    size_t monitor_pack_bytes = 0;
 };
 #define MWB_COPY_TABLE_DESCS 64
 static unsigned long long g_next_serial = 1;
@@ -388,6 +396,7 @@ extern "C" int mwb_destroy(mwb_handle *h) {
     if (h->copy_pairs) hipFree(h->copy_pairs);
     rollout_free(h->rollout);
     learner_free(h->learner);
+    if (h->monitor_mem) hipFree(h->monitor_mem);
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
@@ -1012,6 +1021,119 @@ extern "C" int mwb_rollout_rejected(mwb_handle *h, unsigned long long *rows) {
     HIP_TRY(hipMemcpy(rows, h->rollout.rejected, sizeof(*rows), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemset(h->rollout.rejected, 0, sizeof(*rows)));
     HIP_TRY(hipDeviceSynchronize());
+    return MWB_OK;
+}
+
+// ------------------------------------------------------------------------------------ episode monitor
+// returns, lengths, the log of the last episodes, evaluation quotas; the arithmetic is mwb_monitor_map.h, the kernels mwb_monitor.hip
+static_assert(sizeof(mwb_monitor_counts) == 32, "two u64 counters, then the four u32 the kernels index with MWB_MON_*");
+static_assert(offsetof(mwb_monitor_counts, dropped) == 8 * MWB_MON_DROPPED && offsetof(mwb_monitor_counts, remaining) == 16 + 4 * MWB_MON_REMAINING &&
+              offsetof(mwb_monitor_counts, quota) == 16 + 4 * MWB_MON_QUOTA && offsetof(mwb_monitor_counts, last_base) == 16 + 4 * MWB_MON_BASE &&
+              offsetof(mwb_monitor_counts, last_count) == 16 + 4 * MWB_MON_COUNT, "struct mwb_monitor_counts is what the kernels write");
+
+extern "C" int mwb_monitor_enable(mwb_handle *h, int capacity, int quota_max) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_monitor_enable: null handle");
+    if (capacity < 1 || capacity > MWB_MONITOR_MAX_CAPACITY) return set_err(MWB_EINVAL, "mwb_monitor_enable: capacity must lie in 1 .. " + std::to_string(MWB_MONITOR_MAX_CAPACITY));
+    if (quota_max < 0 || quota_max > MWB_MONITOR_MAX_QUOTA) return set_err(MWB_EINVAL, "mwb_monitor_enable: quota_max must lie in 0 .. " + std::to_string(MWB_MONITOR_MAX_QUOTA));
+    if (h->cfg.no_auto_reset) return set_err(MWB_EINVAL, "mwb_monitor_enable: the handle was created with no_auto_reset: a finished env stops, no later step belongs to an episode");
+    if (h->monitor_on) return set_err(MWB_ESTATE, "mwb_monitor_enable: already enabled");
+    USE_DEVICE(h->cfg.device);
+    MwbMonitor m = {};
+    m.N = h->dev.N; m.capacity = capacity; m.Q = quota_max; m.n_waves = (int)(((size_t)m.N + 63) / 64);
+    const size_t N = (size_t)m.N, C = (size_t)capacity, QN = (size_t)quota_max * N, NW = (size_t)m.n_waves;
+    // two passes over one list of pieces: sizes first, pointers after the allocation.  The first six are the host pack and lie
+    // back to back (8-byte pieces first, so every piece is aligned to its element); every later piece starts on 256 bytes
+    size_t at = 0;
+    char *base = nullptr;
+    auto piece = [&](auto *&p, size_t bytes, bool packed) {
+        if (!packed) at = (at + 255) & ~(size_t)255;
+        if (base) p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at);
+        at += bytes;
+    };
+    size_t pack_bytes = 0;
+    auto carve = [&]() {
+        at = 0;
+        piece(m.last_return, N * 8, true); piece(m.last_len, N * 4, true); piece(m.last_calls, N * 4, true);
+        piece(m.counts64, sizeof(mwb_monitor_counts), true); piece(m.logged, N, true); piece(m.retired, N, true);
+        pack_bytes = at;
+        piece(m.run_return, N * 8, false); piece(m.run_len, N * 4, false); piece(m.run_calls, N * 4, false); piece(m.finished, N * 4, false);
+        piece(m.partial, N, false);
+        piece(m.log_return, C * 8, false); piece(m.log_len, C * 4, false); piece(m.log_calls, C * 4, false); piece(m.log_env, C * 4, false);
+        piece(m.tab_return, QN * 8, false); piece(m.tab_len, QN * 4, false);
+        piece(m.wave_ballot, NW * 8, false); piece(m.wave_base, NW * 4, false); piece(m.wave_aux, NW * 4, false);
+    };
+    carve();
+    const size_t bytes = at;
+    void *mem = nullptr;
+    hipError_t e = hipMalloc(&mem, bytes);
+    if (e != hipSuccess) return set_err(MWB_ENOMEM, std::string("mwb_monitor_enable: hipMalloc failed: ") + hipGetErrorString(e));
+    base = (char *)mem;
+    carve();
+    m.counts32 = (uint32_t *)(m.counts64 + 2);
+    if (!quota_max) { m.tab_return = nullptr; m.tab_len = nullptr; }
+    int rc = MWB_OK;
+    if ((e = hipMemset(mem, 0, bytes)) != hipSuccess) rc = set_err(MWB_EHIP, std::string("mwb_monitor_enable: hipMemset failed: ") + hipGetErrorString(e));
+    if (rc == MWB_OK) {   // quota 0, remaining = N, the table as NaN / -1
+        mwb_launch_monitor_quota(m, 0, nullptr);
+        rc = check_launch("monitor_quota_kernel");
+    }
+    if (rc == MWB_OK && hipDeviceSynchronize() != hipSuccess) rc = set_err(MWB_EHIP, "mwb_monitor_enable: hipDeviceSynchronize failed");
+    if (rc != MWB_OK) { hipFree(mem); return rc; }   // the handle is as it was
+    h->monitor = m; h->monitor_mem = mem; h->monitor_pack = m.last_return; h->monitor_pack_bytes = pack_bytes; h->monitor_on = true;
+    return MWB_OK;
+}
+
+extern "C" int mwb_monitor_update(mwb_handle *h, const uint8_t *skip_mask_dev, const double *reward64_dev, const uint8_t *done_dev,
+                                  const int32_t *taken_dev, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_monitor_update: null handle");
+    if (!h->monitor_on) return set_err(MWB_ESTATE, "mwb_monitor_update: call mwb_monitor_enable first");
+    USE_DEVICE(h->cfg.device);
+    // the sub-steps of the call: the repeat's count if that was the last pass, 1 (NULL) after a plain step - the rollout's rule
+    const int32_t *taken = taken_dev ? taken_dev : (h->last_pass_repeat ? h->rep_taken : nullptr);
+    mwb_launch_monitor_update(h->monitor, skip_mask_dev, reward64_dev ? reward64_dev : h->dev.reward64, done_dev ? done_dev : h->dev.done, taken,
+                              (hipStream_t)stream);
+    return check_launch("monitor update kernels");
+}
+
+extern "C" int mwb_monitor_clear(mwb_handle *h, const uint8_t *mask_dev, int partial, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_monitor_clear: null handle");
+    if (!h->monitor_on) return set_err(MWB_ESTATE, "mwb_monitor_clear: call mwb_monitor_enable first");
+    USE_DEVICE(h->cfg.device);
+    mwb_launch_monitor_clear(h->monitor, mask_dev, partial != 0, (hipStream_t)stream);
+    return check_launch("monitor_clear_kernel");
+}
+
+extern "C" int mwb_monitor_quota(mwb_handle *h, int quota, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_monitor_quota: null handle");
+    if (!h->monitor_on) return set_err(MWB_ESTATE, "mwb_monitor_quota: call mwb_monitor_enable first");
+    if (quota < 0 || quota > h->monitor.Q) return set_err(MWB_EINVAL, "mwb_monitor_quota: quota must lie in 0 .. quota_max = " + std::to_string(h->monitor.Q));
+    USE_DEVICE(h->cfg.device);
+    mwb_launch_monitor_quota(h->monitor, quota, (hipStream_t)stream);
+    return check_launch("monitor_quota_kernel");
+}
+
+extern "C" int mwb_monitor_info(mwb_handle *h, struct mwb_monitor_info *out) {
+    if (!h || !out) return set_err(MWB_EINVAL, "mwb_monitor_info: null argument");
+    if (!h->monitor_on) return set_err(MWB_ESTATE, "mwb_monitor_info: call mwb_monitor_enable first");
+    const MwbMonitor &m = h->monitor;
+    memset(out, 0, sizeof(*out));
+    out->run_return = m.run_return; out->last_return = m.last_return;
+    out->run_len = m.run_len; out->run_calls = m.run_calls; out->last_len = m.last_len; out->last_calls = m.last_calls; out->finished = m.finished;
+    out->partial = m.partial; out->retired = m.retired; out->logged = m.logged;
+    out->log_return = m.log_return; out->log_len = m.log_len; out->log_calls = m.log_calls; out->log_env = m.log_env;
+    out->tab_return = m.tab_return; out->tab_len = m.tab_len;
+    out->counts = m.counts64; out->host_pack = h->monitor_pack; out->host_pack_bytes = h->monitor_pack_bytes;
+    out->num_envs = m.N; out->capacity = m.capacity; out->quota_max = m.Q;
+    return MWB_OK;
+}
+
+extern "C" int mwb_monitor_read(mwb_handle *h, struct mwb_monitor_counts *out) {
+    if (!h || !out) return set_err(MWB_EINVAL, "mwb_monitor_read: null argument");
+    memset(out, 0, sizeof(*out));
+    if (!h->monitor_on) return set_err(MWB_ESTATE, "mwb_monitor_read: call mwb_monitor_enable first");
+    USE_DEVICE(h->cfg.device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, h->monitor.counts64, sizeof(*out), hipMemcpyDeviceToHost));
     return MWB_OK;
 }
 

@@ -388,6 +388,36 @@ void mwb_launch_rollout_returns(const MwbRollout &r, const MwbLearner &l, int mo
 void mwb_launch_rollout_gather_cols(const MwbRollout &r, const MwbLearner &l, const int64_t *index, int count, const float *adv_src,
                                     float *out_f32, int64_t *out_action, hipStream_t s);
 
+// ---- the episode monitor (mwb_monitor_enable; mwb_monitor_map.h says where a record of the log lives).  Passed by value to the
+// kernels of mwb_monitor.hip.  Nothing of it lives on the host: the counters, the quota and the scan's scratch are device memory,
+// so a captured graph of an update can be replayed.
+#define MWB_MON_TOTAL 0       // counts64[]: episodes ever appended to the log
+#define MWB_MON_DROPPED 1     //             episodes that ended with `partial` set
+#define MWB_MON_REMAINING 0   // counts32[]: envs not retired
+#define MWB_MON_QUOTA 1       //             the per-env quota (0 = none)
+#define MWB_MON_BASE 2        //             slot of rank 0 of the last pass
+#define MWB_MON_COUNT 3       //             loggable episodes of the last pass
+struct MwbMonitor {
+    int N, capacity, Q, n_waves;   // envs, log records, rows of the table, ceil(N / 64)
+    double *run_return, *last_return;
+    int32_t *run_len, *run_calls, *last_len, *last_calls, *finished;
+    uint8_t *partial, *retired, *logged;   // logged: the last update appended an episode of env e
+    double *log_return;
+    int32_t *log_len, *log_calls, *log_env;
+    double *tab_return;                    // [Q][N]
+    int32_t *tab_len;                      // [Q][N]
+    unsigned long long *counts64;          // [2] MWB_MON_TOTAL, MWB_MON_DROPPED
+    uint32_t *counts32;                    // [4] MWB_MON_REMAINING .. MWB_MON_COUNT
+    unsigned long long *wave_ballot;       // [n_waves] the loggable finishing lanes of wave w in the last pass
+    uint32_t *wave_base;                   // [n_waves] loggable episodes of the last pass in waves before w
+    uint32_t *wave_aux;                    // [n_waves] dropped episodes | envs not retired << 8 of wave w in the last pass
+};
+// launch wrappers implemented in mwb_monitor.hip.  update: the three launches of one pass; reward / done as given, taken = NULL
+// counts 1 per call.  clear: mask = NULL names every env.  quota: validated by the API (0 .. Q)
+void mwb_launch_monitor_update(const MwbMonitor &m, const uint8_t *skip, const double *reward, const uint8_t *done, const int32_t *taken, hipStream_t s);
+void mwb_launch_monitor_clear(const MwbMonitor &m, const uint8_t *mask, int partial, hipStream_t s);
+void mwb_launch_monitor_quota(const MwbMonitor &m, int quota, hipStream_t s);
+
 // launch wrappers implemented in mwb_kernels.hip
 void mwb_launch_step(const MwbDev &d, const int32_t *actions, const uint8_t *skip_mask, hipStream_t s);   // entity tasks: step_ents_kernel
 void mwb_launch_clear_list(const MwbDev &d, hipStream_t s);

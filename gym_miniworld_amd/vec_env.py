@@ -6,6 +6,7 @@ pytorch-a2c-ppo-acktr/envs.py:57-165 (make_vec_envs -> TransposeImage -> VecPyTo
 VecPyTorchFrameStack) - but the N environments live in one HIP handle instead of N processes, and
 observations never leave the GPU.
 """
+import time
 from abc import ABC, abstractmethod
 
 import numpy as np
@@ -75,11 +76,18 @@ class LazyInfos:
     exposed too, so that a trainer can replace its per-env loop
         for info in infos: _feature.append(info["feature"])          (pytorch-a2c-ppo-acktr/main.py:612-617)
     by `infos.feature`:  goal_pos [N,3] float64 or None, feature [N,2] float64 or None, skipped bool [N] or None, and with
-    frame_skip taken int32 [N] (info['taken']: the sub-steps behind the transition, for gamma ** taken) or None."""
+    frame_skip taken int32 [N] (info['taken']: the sub-steps behind the transition, for gamma ** taken) or None.
+    With a monitor (MiniWorldVecEnv(monitor=K)): episode_r float64 [N] and episode_l int32 [N], the return and the length in env
+    steps of the episode that ended last in every env, and episode_logged bool [N], the envs whose episode ended - and was logged -
+    in this step: for those info['episode'] = {'r', 'l', 't'} as the reference's bench.Monitor wrapper delivers it (main.py:262;
+    from memory, parity unpinned: the wrapper belongs to the un-vendored `baselines` and rounds r and t to 6 places - nothing is
+    rounded here).  An env whose episode's start the monitor did not see (a copy_envs destination) carries no 'episode'."""
 
-    def __init__(self, n, goal_pos=None, feature=None, skipped=None, default_feature=False, health=None, taken=None):
+    def __init__(self, n, goal_pos=None, feature=None, skipped=None, default_feature=False, health=None, taken=None,
+                 episode_r=None, episode_l=None, episode_logged=None, episode_t=0.0):
         self.n, self.goal_pos, self.skipped = n, goal_pos, skipped
         self.taken = taken
+        self.episode_r, self.episode_l, self.episode_logged, self.episode_t = episode_r, episode_l, episode_logged, episode_t
         self.health = health   # CollectHealth: info['health'] (collecthealth.py:75), float64 [N] or None
         self._task_feature = feature is not None
         self.feature = feature if feature is not None else (np.zeros((n, 2)) if default_feature else None)
@@ -97,6 +105,8 @@ class LazyInfos:
         if self.skipped is not None and self.skipped[i]:
             return _DUMMY_INFO
         info = {}
+        if self.episode_logged is not None and self.episode_logged[i]:
+            info["episode"] = {"r": float(self.episode_r[i]), "l": int(self.episode_l[i]), "t": self.episode_t}
         if self.goal_pos is not None:
             info["goal_pos"] = self.goal_pos[i].copy()
         if self.health is not None:
@@ -138,6 +148,12 @@ class MiniWorldVecEnv(VecEnv):
                        actions it was given (int32 or int64, as handed over) and, with frame_skip=k, the sub-steps it took; the
                        trainer calls envs.rollout.insert(value, log_prob) after the step, then compute_returns(...) and
                        feed_forward_generator(...): no second storage object
+    monitor=K       -> the trainer's record of its own progress kept on the device (BatchedMiniWorld.monitor_enable): `envs.monitor`
+                       holds the running return / length of every env and the log of the last K episodes - the deque(maxlen=100)
+                       and the loop over `done` of main.py:141,167-169, with the return summed per episode - updated inside every
+                       step (part of the captured graph with graph=True); envs.monitor.stats() is what the trainer prints.  An env
+                       whose episode ended carries info['episode'] = {'r', 'l', 't'}; monitor_quota_max=Q (0 .. 64, default 8) sizes
+                       the per-env evaluation table: the most episodes per env evaluate() can be asked for
     feature_info    -> every info dict carries "feature" (length-2 zeros) as the fork's PPO loop
                        requires (pytorch-a2c-ppo-acktr/main.py:614-619)
     graph=True      -> after two eager steps the whole step (mwb_step's kernels on both streams, the frame-stack /
@@ -152,7 +168,7 @@ class MiniWorldVecEnv(VecEnv):
 
     def __init__(self, env_id, num_envs, seed=1, device=0, domain_rand=False, transpose=True, to_float=True,
                  frame_stack=0, torch_api=True, feature_info=False, first_env_index=0, graph=False, greyscale=False, frame_skip=1,
-                 rollout_steps=0, rollout_learner=False, **kwargs):
+                 rollout_steps=0, rollout_learner=False, monitor=0, monitor_quota_max=8, **kwargs):
         import torch
         from .batch import BatchedMiniWorld
         from . import _lib
@@ -192,6 +208,9 @@ class MiniWorldVecEnv(VecEnv):
         # the trainer's RolloutStorage on the device: pushed by reset() and by the device part of every step
         self.rollout = b.rollout_enable(int(rollout_steps), nstack=self.nstack or 1, grey=self.greyscale,
                                         learner=bool(rollout_learner)) if rollout_steps else None
+        # the trainer's record of its own progress on the device: updated by the device part of every step
+        self.monitor = b.monitor_enable(int(monitor), quota_max=int(monitor_quota_max)) if monitor else None
+        self._t0 = time.time()
         VecEnv.__init__(self, num_envs, Box(0, 255, shape, np.float32 if to_float else np.uint8), Discrete(b.n_actions))
         self.device = b.device
         self.feature_info = feature_info
@@ -216,6 +235,16 @@ class MiniWorldVecEnv(VecEnv):
         self._h_feat = part("feature", np.float32, 2 * n).reshape(n, 2) if (b.has_features or b.has_health) else None
         self._h_skip = pin((num_envs,), torch.uint8)
         self._h_taken = pin((num_envs,), torch.int32) if self.frame_skip > 1 else None   # filled by a copy of its own, beside the pack's
+        self._h_mon = None   # the monitor's host pack: one more copy beside the pack's
+        if self.monitor is not None:
+            mo = self.monitor.host_pack_offsets
+            self._h_mon = pin((int(self.monitor.host_pack.numel()),), torch.uint8)
+            hm = self._h_mon.numpy()
+            self._h_ep_r = np.frombuffer(hm, dtype=np.float64, count=n, offset=mo["last_return"])
+            self._h_ep_l = np.frombuffer(hm, dtype=np.int32, count=n, offset=mo["last_len"])
+            self._h_ep_logged = np.frombuffer(hm, dtype=np.uint8, count=n, offset=mo["logged"])
+            self._h_retired = np.frombuffer(hm, dtype=np.uint8, count=n, offset=mo["retired"])
+            self._h_mon_counts = np.frombuffer(hm, dtype=np.uint32, count=8, offset=mo["counts"])   # struct mwb_monitor_counts
         self._ev = torch.cuda.Event()
         self._skip_host = None
         self._use_graph, self._graph, self._eager_steps = bool(graph), None, 0
@@ -255,8 +284,12 @@ class MiniWorldVecEnv(VecEnv):
             ro.push()
             if ro.learner:
                 ro.insert(action=a)   # the actions of the transition just pushed; value / log_prob are the trainer's to insert
+        if self.monitor is not None:
+            self.monitor.update(skip_mask=skip)   # three small launches right behind the step: reward64, done and `taken` as it left them
         obs = self._obs_out(done=b.done)
         self._h_pack.copy_(b.pack[:self._pack_need], non_blocking=True)   # one copy: the small outputs share an allocation
+        if self._h_mon is not None:
+            self._h_mon.copy_(self.monitor.host_pack, non_blocking=True)
         if self._h_taken is not None:
             self._h_taken.copy_(b.taken, non_blocking=True)   # same stream, ahead of step_wait's one wait
         return obs
@@ -317,14 +350,18 @@ class MiniWorldVecEnv(VecEnv):
             rews = self._h_rew.copy()
         sk = self._skip_host
         tk = self._h_taken.numpy().copy() if self._h_taken is not None else None   # info['taken']
+        ep = {}
+        if self._h_mon is not None:   # info['episode'] of the envs whose episode ended, and was logged, in this step
+            ep = dict(episode_r=self._h_ep_r.copy(), episode_l=self._h_ep_l.copy(), episode_logged=self._h_ep_logged.astype(bool) & dones,
+                      episode_t=time.time() - self._t0)
         if b.has_health:   # CollectHealth: info['health'] (delivered in feature[:, 0])
-            infos = LazyInfos(self.num_envs, health=self._h_feat[:, 0].astype(np.float64), skipped=sk, default_feature=self.feature_info, taken=tk)
+            infos = LazyInfos(self.num_envs, health=self._h_feat[:, 0].astype(np.float64), skipped=sk, default_feature=self.feature_info, taken=tk, **ep)
         elif b.has_goal_pos:   # the T-maze family: info['goal_pos'] (tmaze.py:66,206) and, where produced, info['feature']
             infos = LazyInfos(self.num_envs, goal_pos=self._h_goal.copy(),
                               feature=self._h_feat.astype(np.float64) if self._h_feat is not None else None,
-                              skipped=sk, default_feature=self.feature_info, taken=tk)
-        elif tk is not None or (sk is not None and sk.any()):
-            infos = LazyInfos(self.num_envs, skipped=sk, default_feature=self.feature_info, taken=tk)
+                              skipped=sk, default_feature=self.feature_info, taken=tk, **ep)
+        elif ep or tk is not None or (sk is not None and sk.any()):
+            infos = LazyInfos(self.num_envs, skipped=sk, default_feature=self.feature_info, taken=tk, **ep)
         else:
             infos = self._infos_plain
         return obs, rews, dones, infos
@@ -342,9 +379,51 @@ class MiniWorldVecEnv(VecEnv):
             return b.grey
         return b.obs.float() if self.to_float else b.obs
 
+    @property
+    def monitor_remaining(self):
+        """envs not yet retired, as of the last step_wait() (the monitor's counter, delivered with the step's one wait)"""
+        return int(self._h_mon_counts[4])
+
+    @property
+    def monitor_retired(self):
+        """bool [N] on the host: the monitor's `retired` as of the last step_wait() - the next step's `mask`"""
+        return self._h_retired.astype(bool)
+
     def close(self):
         self._graph = None
         self.batch.close()
+
+
+def evaluate(envs, act, episodes_per_env=1, max_calls=None):
+    """Evaluate a policy on a vectorised env: every env plays exactly `episodes_per_env` episodes, then retires (it is named in
+    the `mask` of every later step and stands still).  act(obs) -> actions for envs.step.  Returns (returns, lengths): float64
+    and int32 [episodes_per_env, N] device tensors, env e's j-th episode in [j, e]; lengths in env steps.
+
+    Why per env and not the reference's "first K episodes to finish" (`while len(eval_episode_rewards) < 10`,
+    pytorch-a2c-ppo-acktr/main.py:248-262): on N parallel envs the episodes that finish first are the short ones - in a maze
+    the successes, while the time-outs are still running - so the first K over-sample success.  A fixed number per env is an
+    unbiased sample of the policy's episodes; the skip mask of the step kernels is what lets an env wait for the others.
+
+    Needs MiniWorldVecEnv(monitor=K, monitor_quota_max >= episodes_per_env).  Sets the quota, resets, and steps until the
+    monitor's `remaining` - read with every step's one wait, no extra synchronisation - is 0, or after max_calls steps (then
+    the unfinished cells hold NaN / -1).  The quota stays set; envs.monitor.set_quota(0) before training goes on."""
+    mon = envs.monitor
+    if mon is None:
+        raise ValueError("evaluate needs a monitor: MiniWorldVecEnv(..., monitor=K)")
+    q = int(episodes_per_env)
+    if not 1 <= q <= mon.quota_max:
+        raise ValueError("evaluate: episodes_per_env %d outside 1 .. monitor_quota_max = %d" % (q, mon.quota_max))
+    mon.set_quota(q)
+    obs = envs.reset()
+    mask, calls = None, 0
+    while max_calls is None or calls < max_calls:
+        obs = envs.step(act(obs), mask=mask)[0]
+        calls += 1
+        if envs.monitor_remaining == 0:
+            break
+        retired = envs.monitor_retired
+        mask = retired if retired.any() else None
+    return mon.tab_return[:q].clone(), mon.tab_len[:q].clone()
 
 
 def make_vec_envs(env_name, seed, num_processes, gamma=None, log_dir=None, add_timestep=False, device=None,
@@ -354,4 +433,4 @@ def make_vec_envs(env_name, seed, num_processes, gamma=None, log_dir=None, add_t
     import torch
     dev = torch.device(device if device is not None else "cuda:0")
     return MiniWorldVecEnv(env_name, num_processes, seed=seed, device=dev.index or 0, transpose=True, to_float=True,
-                           frame_stack=4, torch_api=True, feature_info=True, **kwargs)
+                           frame_stack=4, torch_api=True, feature_info=True, **kwargs)   # (monitor=K rides in kwargs; log_dir stays ignored)

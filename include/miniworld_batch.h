@@ -512,6 +512,72 @@ struct mwb_rollout_learner_info {
 };
 int mwb_rollout_learner_info(mwb_handle *h, struct mwb_rollout_learner_info *out);
 
+/* ---- episode monitor on the device: returns, lengths, the log of the last episodes, evaluation quotas ---------- */
+/* replaces: the trainer's record of its own progress - `episode_rewards = deque(maxlen=100)` filled by a Python loop over every
+ * env after every step (pytorch-a2c-ppo-acktr/main.py:141,167-169), which appends the LAST step's reward of a finished env (its own
+ * comment: "works only for environments with sparse rewards") - and the bench.Monitor wrapper envs.py:45 comments out, whose
+ * info['episode'] the evaluation loop waits for (main.py:248-262).  The monitor keeps, per env, the float64 sum of the rewards of
+ * the running episode (one add per update, from 0.0: the order Python's sum takes), its length in env steps (sub-steps under
+ * mwb_step_repeat) and in step calls; the episode that ended most recently; a ring of the last `capacity` episodes in the order
+ * that loop appends them (pass by pass, increasing env index inside a pass; csrc/mwb_monitor_map.h has the arithmetic); and, for
+ * evaluation, a table of every env's first quota_max episodes with a per-env quota after which an env is `retired` - the mask a
+ * caller hands to the next step as its skip mask, so that "K episodes per env" replaces the biased "first K episodes to finish".
+ * Opt-in: a handle that never calls mwb_monitor_enable launches exactly what it launched before.  Everything, the counters and
+ * the quota included, lives on the device: an update can be captured into a graph together with the step.
+ *
+ * mwb_monitor_enable (replaces deque(maxlen=capacity), main.py:141): capacity in 1 .. 65536, quota_max in 0 .. 64, MWB_EINVAL
+ * otherwise and for a handle created with no_auto_reset (a finished env stops there; what a later step means for an episode is
+ * undefined).  MWB_ESTATE: already enabled.  All accumulators and counters start at zero, the table as NaN / -1, quota 0,
+ * remaining = num_envs.  mwb_destroy frees it. */
+int mwb_monitor_enable(mwb_handle *h, int capacity, int quota_max);
+/* replaces: one turn of the loop main.py:167-169, with the return summed per episode.  With reward64_dev / done_dev / taken_dev
+ * NULL it reads the handle's own reward64 and done outputs and, for the sub-steps of the call, the buffer of mwb_repeat_taken if
+ * the last pass on the handle was an mwb_step_repeat, else 1 (the rule of the rollout's `taken` column, remembered on the host the
+ * same way).  A non-NULL array (device f64 / u8 / i32 [num_envs]) stands in for that output: for a wrapper that shapes rewards.
+ * skip_mask_dev (u8 [num_envs] or NULL): the skip mask the step was given.  For every env with skip_mask[e] == 0, in this order:
+ * run_return += reward; run_len += taken; run_calls += 1; if done: with `partial` set the episode is counted in `dropped`, else
+ * last_* are written, the episode is appended to the log, cell [finished[e]][e] of the table is written if finished[e] < quota_max
+ * and finished[e] grows by one; then the three accumulators are zeroed and `partial` is cleared.  A skipped env is left untouched
+ * (its reward of -99 enters no return).  After the pass retired[e] = quota > 0 && finished[e] >= quota and `remaining` counts the
+ * envs with retired == 0.  Three small launches on `stream`; nothing is read back.  MWB_ESTATE before mwb_monitor_enable. */
+int mwb_monitor_update(mwb_handle *h, const uint8_t *skip_mask_dev, const double *reward64_dev, const uint8_t *done_dev,
+                       const int32_t *taken_dev, void *stream);
+/* replaces: nothing the reference has (its envs are never reset or copied mid-episode).  Zeroes the accumulators of the envs
+ * mask_dev (u8 [num_envs], NULL = all) names.  partial == 0: they start a fresh episode (after an mwb_reset).  partial != 0:
+ * they are now in the middle of an episode whose start the monitor did not see (the destinations of an mwb_copy_envs): that
+ * episode is dropped, not logged, when it ends. */
+int mwb_monitor_clear(mwb_handle *h, const uint8_t *mask_dev, int partial, void *stream);
+/* replaces: `while len(eval_episode_rewards) < 10` (main.py:248): sets the per-env quota, 0 .. quota_max (MWB_EINVAL otherwise),
+ * 0 = none, nobody retires.  Zeroes finished and retired, sets remaining = num_envs and refills the table with NaN / -1; the
+ * running accumulators and the log are not touched. */
+int mwb_monitor_quota(mwb_handle *h, int quota, void *stream);
+/* the monitor's device arrays (fixed for the handle's lifetime), for zero-copy views.  `host_pack` is one contiguous piece of
+ * host_pack_bytes that holds what a host-side consumer wants after every step - last_return | last_len | last_calls | counts |
+ * logged | retired, in this order - so that one copy delivers it.  counts: struct mwb_monitor_counts as it lies on the device. */
+struct mwb_monitor_info {
+    double *run_return, *last_return;                                /* f64 [N] */
+    int32_t *run_len, *run_calls, *last_len, *last_calls, *finished; /* i32 [N] */
+    uint8_t *partial, *retired;                                      /* u8 [N] */
+    uint8_t *logged;                  /* u8 [N]: the last update appended an episode of env e (its last_* are that episode) */
+    double *log_return;               /* f64 [capacity] */
+    int32_t *log_len, *log_calls, *log_env;   /* i32 [capacity] */
+    double *tab_return;               /* f64 [quota_max][N]; NULL when quota_max == 0 */
+    int32_t *tab_len;                 /* i32 [quota_max][N] */
+    void *counts;
+    void *host_pack;
+    size_t host_pack_bytes;
+    int32_t num_envs, capacity, quota_max, pad;
+};
+int mwb_monitor_info(mwb_handle *h, struct mwb_monitor_info *out);   /* MWB_ESTATE before mwb_monitor_enable */
+/* total: episodes ever appended to the log (ring slot = total % capacity); dropped: episodes that ended with `partial` set;
+ * remaining: envs not retired; quota: as mwb_monitor_quota set it */
+struct mwb_monitor_counts {
+    unsigned long long total, dropped;
+    uint32_t remaining, quota;
+    uint32_t last_base, last_count;   /* of the last update: the slot of its first episode and how many it finished */
+};
+int mwb_monitor_read(mwb_handle *h, struct mwb_monitor_counts *out);   /* synchronous */
+
 /* World generation cannot fail for the four tasks with sane arguments; if it ever does (a portal outside
  * its wall, more than one portal on an edge, a placement that finds no free spot in 100000 draws - the
  * reference would assert or spin) the kernel flags it. Synchronous: returns MWB_ESTATE if any env of the
