@@ -2477,6 +2477,46 @@ __device__ __forceinline__ void sample_texture(const uint32_t *__restrict__ texe
 #pragma unroll
     for (int k = 0; k < 3; k++) rgb[k] = fmaf(c1[k] - c0[k], fr, c0[k]);
 }
+// sample_texture in two halves with the texel round trip between them (the fixed-shape bulk kernels' interior batches,
+// RenderCtx::interior_issue / interior_finish).  A TexTap is what crosses: the two footprints - possibly still on their way - and
+// what the blend needs besides them.  sample_issue is sample_texture up to and including its two loads, sample_finish the rest:
+// the same expressions in the same order, so the same bits (tests/test_gpu_render_fixed.py, tests/test_gpu_render_pipeline.py
+// step such a kernel beside the generic one).  Copies, not a split of sample_texture itself: every other caller's kernel must
+// come out of the compiler as it did (tests/test_kernel_resources_unchanged.py), and inlined through a split they did not.
+struct TexTap { uint4 f0, f1; float a0, b0, a1, b1, fr; };
+__device__ __forceinline__ void sample_issue(const uint32_t *__restrict__ texels, const TexLds &T, float s, float t, float sx,
+                                             float tx, float sy, float ty, bool valid, TexTap &tap) {
+    const int4 dims = *(const int4 *)&T.w;   // w h n_levels sc_s(bits)
+    const int maxl = dims.z - 1;
+    const float fw = (float)dims.x, fh = (float)dims.y;
+    const float dsdx = (sx - s) * fw, dtdx = (tx - t) * fh;
+    const float dsdy = (sy - s) * fw, dtdy = (ty - t) * fh;
+    const float r1 = fmaf(dsdx, dsdx, dtdx * dtdx), r2 = fmaf(dsdy, dsdy, dtdy * dtdy);
+    const float rho2 = r1 > r2 ? r1 : r2;
+    const float lg = 0.5f * __log2f(fmaxf(rho2, 1.0f));
+    const float lambda = (valid && rho2 < INFINITY) ? lg : (float)maxl;
+    float ws = s - floorf(s), wt = t - floorf(t);
+    ws = (ws >= 0.0f && ws < 1.0f) ? ws : 0.0f;
+    wt = (wt >= 0.0f && wt < 1.0f) ? wt : 0.0f;
+    const float fl = floorf(lambda);
+    int l0 = (int)fl; l0 = l0 > maxl ? maxl : l0;
+    const int l1 = l0 + 1 > maxl ? maxl : l0 + 1;
+    tap.fr = (l0 == maxl) ? 0.0f : lambda - fl;
+    int w0 = dims.x >> l0; w0 = w0 < 1 ? 1 : w0;
+    int h0 = dims.y >> l0; h0 = h0 < 1 ? 1 : h0;
+    int w1 = dims.x >> l1; w1 = w1 < 1 ? 1 : w1;
+    int h1 = dims.y >> l1; h1 = h1 < 1 ? 1 : h1;
+    const uint32_t e0 = footprint_index(T.off[l0], w0, h0, ws, wt, tap.a0, tap.b0);
+    const uint32_t e1 = footprint_index(T.off[l1], w1, h1, ws, wt, tap.a1, tap.b1);
+    tap.f0 = footprint_load(texels, e0); tap.f1 = footprint_load(texels, e1);
+}
+__device__ __forceinline__ void sample_finish(const TexTap &tap, float *rgb) {
+    float c0[3], c1[3];
+    bilinear_blend(tap.f0, tap.a0, tap.b0, c0);
+    bilinear_blend(tap.f1, tap.a1, tap.b1, c1);
+#pragma unroll
+    for (int k = 0; k < 3; k++) rgb[k] = fmaf(c1[k] - c0[k], tap.fr, c0[k]);
+}
 
 // texture coordinates where ray (o, dv) meets the plane {axis = plane}; false if behind / parallel
 __device__ __forceinline__ bool plane_texcoord(int axis, float plane, float u_org, float u_scale, float sc_t, const float *o,
@@ -2504,6 +2544,7 @@ struct ShapeRuntime {
     __device__ __forceinline__ static int debug(const MwbDev &d) { return d.debug_flags; }
     __device__ __forceinline__ static int exp(const MwbDev &d) { return d.exp_flags; }
     __device__ __forceinline__ static bool has_depth(const float *depth) { return depth != nullptr; }
+    static constexpr bool pipelined = false;   // an interior batch fetches, waits and blends in one call (pixel_interior)
 };
 template <int W_, int H_, int LAYOUT, bool DEPTH>
 struct ShapeFixed {
@@ -2514,6 +2555,9 @@ struct ShapeFixed {
     __device__ __forceinline__ static constexpr int debug(const MwbDev &) { return 0; }
     __device__ __forceinline__ static constexpr int exp(const MwbDev &) { return 0; }
     __device__ __forceinline__ static constexpr bool has_depth(const float *) { return DEPTH; }
+    // an interior batch's footprints may stay in flight until the wave's next batch is due (render_env's PIPE).  Not with depth:
+    // built that way, all eight such instantiations spilled 52 - 320 B/lane (the tap's 15 registers on top of 85 - 89)
+    static constexpr bool pipelined = !DEPTH;
 };
 
 template <int NBOX, bool POLY, class SP = ShapeRuntime>
@@ -3291,6 +3335,51 @@ struct RenderCtx {
         }
         write_pixel<true>(px, py, col, true, t_s0);
     }
+
+    // pixel_interior in two halves, for the kernels that finish an interior batch one batch late (render_env's PIPE: rectangle
+    // rooms, one box, no depth).  interior_issue is shade<true> up to and including the two footprint loads - key unpack, surface
+    // set-up, the three texture coordinates, LOD, the two entries - and leaves the tap; interior_finish is the rest: the blends,
+    // the level lerp, the lit colour (found again from the key, as shade_poly does after its fetch) and the pixel.  Between the
+    // two only the tap, the pixel and the key are live.  The expressions are shade's, in shade's order (see sample_issue on why
+    // these are copies).
+    __device__ __forceinline__ void interior_issue(int px, int py, uint32_t key, TexTap &tap) const {
+        static_assert(!POLY, "shade's rectangle-room set-up");
+        const float cx = (float)px + 0.5f, cy = (float)(H - 1 - py) + 0.5f;
+        const uint32_t kind = key & 7u, side = (key >> 3) & 3u;
+        const float *r = rooms + __umul24(key >> 6, MWB_ROOM_WORDS);
+        const float4 rect = *(const float4 *)(r + RW_MINX);   // min_x max_x min_z max_z
+        const float height = r[RW_HEIGHT];
+        const uint32_t texw = (uint32_t)__float_as_int(r[RW_TEX]);
+        const float u_org_w = r[RW_SIDE0 + RW_SIDE_WORDS * side + RS_UORG];
+        const bool wall = kind == KIND_WALL, floor_ = kind == KIND_FLOOR;
+        const uint32_t tex_id = (wall ? texw : floor_ ? (texw >> 8) : (texw >> 16)) & 255u;
+        const TexLds &T = tex[tex_id];
+        const bool is_x = wall && !(side & 1u), is_z = wall && (side & 1u);
+        const float wall_plane = side == 0u ? rect.y : side == 2u ? rect.x : side == 3u ? rect.w : rect.z;
+        const int axis = is_x ? 0 : (is_z ? 2 : 1);
+        const float plane = wall ? wall_plane : (floor_ ? 0.0f : height);
+        const float u_org = wall ? u_org_w : 0.0f;
+        const float sc_s = T.sc_s, sc_t = T.sc_t;
+        const float u_scale = (wall && ((texw >> (24 + side)) & 1u)) ? -sc_s : sc_s;
+        float dc[3], dx[3], dy[3];
+        make_ray(cam, cx, cy, dc);
+        neighbour_rays(dc, dx, dy);
+        float s0, t0, s1, t1, s2, t2;
+        plane_texcoord(axis, plane, u_org, u_scale, sc_t, cam.eye, dc, s0, t0);
+        const bool v1 = plane_texcoord(axis, plane, u_org, u_scale, sc_t, cam.eye, dx, s1, t1);
+        const bool v2 = plane_texcoord(axis, plane, u_org, u_scale, sc_t, cam.eye, dy, s2, t2);
+        sample_issue(texels, T, s0, t0, s1, t1, s2, t2, v1 && v2, tap);
+    }
+    __device__ __forceinline__ void interior_finish(int px, int py, uint32_t key, const TexTap &tap) const {
+        static_assert(!POLY && !SP::has_depth(nullptr), "no polygon-room lighting and no depth value here");
+        const uint32_t kind = key & 7u, side = (key >> 3) & 3u;
+        const float *lit = fc + (kind == KIND_WALL ? FC_LIT_WALL + 3 * side : kind == KIND_FLOOR ? FC_LIT_FLOOR : FC_LIT_CEIL);
+        float texel[3], col[3];
+        sample_finish(tap, texel);
+#pragma unroll
+        for (int q = 0; q < 3; q++) col[q] = lit[q] * (texel[q] * (1.0f / 255.0f));
+        write_pixel<true>(px, py, col, true, 1.0f);
+    }
 };
 
 // LDS -> HBM copy of the byte range [begin, end) of the frame with the widest vectors its alignment allows; dst2: a second
@@ -3602,8 +3691,25 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
         return touch;
     };
 
+    // PIPE: an interior batch is finished one batch late.  Where the shape policy allows it and it was measured to pay
+    // (profiles/render_texpipe_ab.txt): the one-box rectangle-room kernels - Maze +1.7 %, FourRooms +1.0 %; the polygon-room kernel
+    // lost 4 % with it, the six-box one 0.6 %, the two-box one was not measured.
+    constexpr bool PIPE = SP::pipelined && NBOX == 1 && !POLY;
+    // the wave's last batch of 64 interior pixels, issued and not yet finished (RenderCtx::interior_issue) - its tap,
+    // its pixels and keys, 15 registers; whether there is one is wave-uniform.  It is finished when the wave's next batch is due -
+    // its footprints have travelled under the corner pass and the 8-sample batches in between - and, the last one, ahead of the
+    // leftover pooling below.
+    TexTap pend_tap = {};
+    uint32_t pend_pix = 0, pend_key = 0;
+    bool pending = false;
+    auto finish_pending = [&]() {
+        if constexpr (PIPE) {
+            if (pending) ctx.interior_finish((int)pend_pix & wmask, (int)pend_pix >> wshift, pend_key, pend_tap);
+            pending = false;
+        }
+    };
     // a classified pixel goes to its per-wave queue; a queue that reaches 64 entries is processed at once (dense lanes)
-    auto emit = [&](int px, int py, bool is_pixel, bool interior, uint32_t key, int skip, uint32_t iboxes) {
+    auto emit =[&](int px, int py, bool is_pixel, bool interior, uint32_t key, int skip, uint32_t iboxes) {
         bool edge = is_pixel && !interior;
         if constexpr (NBOX > MWB_MAX_BOXES) {
             // 8-sample pixels that a mesh may cover queue up apart: their batches walk mesh hierarchies with most lanes busy, while
@@ -3633,7 +3739,17 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
         if (iq_count >= WAVE) {
             iq_count -= WAVE;
             const int q = iq_pix[iq_count + lane];
-            if (!(SP::debug(d) & 4)) ctx.pixel_interior(q & wmask, q >> wshift, iq_key[iq_count + lane]);
+            if constexpr (PIPE) {
+                // the batch before this one is finished first: its tap's registers are free when this batch's loads are issued, so
+                // they land there and nothing waits for them or copies them (issued first, they would have to be moved into the
+                // pending tap's registers afterwards - a wait for them right away)
+                finish_pending();
+                pend_pix = (uint32_t)q; pend_key = iq_key[iq_count + lane];
+                ctx.interior_issue(q & wmask, q >> wshift, pend_key, pend_tap);
+                pending = true;
+            } else {
+                if (!(SP::debug(d) & 4)) ctx.pixel_interior(q & wmask, q >> wshift, iq_key[iq_count + lane]);
+            }
         }
         if (q_count >= WAVE) {
             q_count -= WAVE;
@@ -3816,6 +3932,7 @@ __device__ __forceinline__ void render_env(const MwbDev &d, const int e, const i
     // pixels to the waves from the first up, 8-sample pixels from the last down - instead of every wave
     // running two partly filled batches.
     int *left = cam_room_s + 4;
+    if constexpr (PIPE) finish_pending();   // nothing stays in flight past the item loop
     if (lane == 0) { left[wave] = iq_count; left[n_waves + wave] = q_count; }
     if constexpr (NBOX > MWB_MAX_BOXES) { if (lane == 0) mleft[wave] = mq_count; }
     __syncthreads();
