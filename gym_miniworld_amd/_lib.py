@@ -33,6 +33,8 @@ MAX_REPEAT = 64      # MWB_MAX_REPEAT
 ROLLOUT_GREY = 1     # MWB_ROLLOUT_GREY
 RETURNS_DISCOUNTED, RETURNS_GAE, RETURNS_PSI = 0, 1, 2   # MWB_RETURNS_*
 MONITOR_MAX_CAPACITY, MONITOR_MAX_QUOTA = 65536, 64      # csrc/mwb_monitor_map.h
+END_CLOCK, END_TASK = 1, 2   # MWB_END_*: the bits of the terminal pass's `cause`
+TERMINAL_FLOAT = 1           # MWB_TERMINAL_FLOAT
 
 
 class MwbConfig(ctypes.Structure):
@@ -88,6 +90,12 @@ class MwbMonitorInfo(ctypes.Structure):   # struct mwb_monitor_info
         [("host_pack_bytes", ctypes.c_size_t)] + [(n, ctypes.c_int32) for n in ("num_envs", "capacity", "quota_max", "pad")]
 
 
+class MwbTerminalInfo(ctypes.Structure):   # struct mwb_terminal_info
+    _fields_ = [(n, ctypes.c_void_p) for n in ("cause", "frames", "grey", "row_of", "row_env", "count", "rows")] + \
+               [(n, ctypes.c_size_t) for n in ("frames_bytes", "grey_bytes", "rows_bytes")] + \
+               [(n, ctypes.c_int32) for n in ("capacity", "rows_float", "planes", "nstack")]
+
+
 class MwbMonitorCounts(ctypes.Structure):   # struct mwb_monitor_counts, as it lies on the device
     _fields_ = [("total", ctypes.c_ulonglong), ("dropped", ctypes.c_ulonglong), ("remaining", ctypes.c_uint32), ("quota", ctypes.c_uint32),
                 ("last_base", ctypes.c_uint32), ("last_count", ctypes.c_uint32)]
@@ -106,6 +114,7 @@ EXPORTS = [
     "mwb_rollout_learner_enable", "mwb_rollout_learner_info", "mwb_rollout_insert", "mwb_rollout_returns", "mwb_rollout_gather_cols",
     "mwb_bulk_variant",
     "mwb_monitor_enable", "mwb_monitor_update", "mwb_monitor_clear", "mwb_monitor_quota", "mwb_monitor_info", "mwb_monitor_read",
+    "mwb_terminal_enable", "mwb_terminal_info", "mwb_terminal_dropped", "mwb_rollout_bootstrap",
 ]
 
 _lib = None
@@ -188,6 +197,11 @@ def load():
     L.mwb_monitor_quota.argtypes = [vp, i32, vp]
     L.mwb_monitor_info.argtypes = [vp, ctypes.POINTER(MwbMonitorInfo)]
     L.mwb_monitor_read.argtypes = [vp, ctypes.POINTER(MwbMonitorCounts)]
+    if hasattr(L, "mwb_terminal_enable"):   # (as mwb_bulk_variant below: an older library through MWB_LIB, scripts/bench_terminal.py's leg (a))
+        L.mwb_terminal_enable.argtypes = [vp, i32, ctypes.c_uint]
+        L.mwb_terminal_info.argtypes = [vp, ctypes.POINTER(MwbTerminalInfo)]
+        L.mwb_terminal_dropped.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
+        L.mwb_rollout_bootstrap.argtypes = [vp, vp, ctypes.c_double, vp]
     if hasattr(L, "mwb_bulk_variant"):   # (an older library loaded through MWB_LIB for a kernel A/B has none; build() checks EXPORTS)
         L.mwb_bulk_variant.argtypes = [vp]
     L.mwb_timing_read.argtypes = [vp] +[ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(i32)]

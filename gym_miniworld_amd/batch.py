@@ -316,6 +316,21 @@ class Rollout:
                                               self.batch._stream()))
         self._keep_ret = (np_,)
 
+    def bootstrap_truncated(self, values, gamma):
+        """The time-limit bootstrap (mwb_rollout_bootstrap): rewards[step - 1][e] += gamma ** taken * values[r] for every terminal
+        row r of the last step() whose env e = terminal.row_env[r] ended by the clock alone (terminal.truncated) - a time-out is
+        no terminal state, the return goes on with V(terminal observation).  values: float32 [capacity] or [capacity, 1] on the
+        batch's device, V(terminal.rows); entries behind terminal.count are ignored.  Call after the push() of that step and
+        before the batch's next pass; needs terminal_enable.  Envs whose row was dropped are skipped (terminal.dropped())."""
+        b = self.batch
+        if b.terminal is None:
+            raise ValueError("rollout bootstrap_truncated: the batch has no terminal observations (terminal_enable)")
+        if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.floating, np.integer)) or not np.isfinite(gamma):
+            raise ValueError("rollout bootstrap_truncated: gamma must be a finite number, not %r" % (gamma,))
+        v = self._column("bootstrap_truncated: values", values, b.terminal.capacity, (self.torch.float32,))
+        _lib.check(self.L.mwb_rollout_bootstrap(b.h, ctypes.c_void_p(v.data_ptr()), float(gamma), b._stream()))
+        self._keep_boot = v   # alive until the asynchronous kernel has consumed it
+
     def minibatch(self, index, advantages=None):
         """index[i] = t * N + e with t in 0 .. T - 1 (the flat indices of the reference's [:-1] views) ->
         (obs, actions, returns, masks, old_log_probs, adv, values): obs as gather() returns it, the others [B, 1].  One gather and
@@ -475,6 +490,87 @@ class Monitor:
                     success_rate=int((r > 0).sum()) / n, mean_len=float(ln.sum()) / n)
 
 
+def check_terminal_args(capacity, num_envs, auto_reset=True, stack_args=None, dtype=None):
+    """What terminal_enable refuses before anything is launched (mwb_terminal_enable would answer MWB_EINVAL): raises ValueError
+    for a batch without auto-reset, for a `capacity` that is no integer in 1 .. num_envs (None: num_envs), for a frame stack
+    that is not the fused one, and for a `dtype` other than "uint8" / "float32" or one that contradicts the stack's (the rows of a
+    stacked batch take the stack's dtype).  stack_args: what stack_enable was given, or None.  Returns (capacity, rows are
+    float32)."""
+    if not auto_reset:
+        raise ValueError("terminal_enable: the batch was created with auto_reset=False: its observation is the terminal frame already")
+    if capacity is None:
+        capacity = num_envs
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)):
+        raise ValueError("terminal_enable: capacity must be an integer, not %r" % (capacity,))
+    if not 1 <= int(capacity) <= int(num_envs):
+        raise ValueError("terminal_enable: capacity %d outside 1 .. num_envs = %d" % (capacity, num_envs))
+    if dtype not in (None, "uint8", "float32"):
+        raise ValueError("terminal_enable: dtype must be 'uint8' or 'float32', not %r" % (dtype,))
+    if stack_args is not None:
+        if not stack_args.get("fused"):
+            raise ValueError("terminal_enable: the frame stack is not the fused one (stack_enable(fused=True)): the terminal rows are "
+                             "built from the fused window's history")
+        if dtype is not None and dtype != stack_args["dtype"]:
+            raise ValueError("terminal_enable: dtype %r, but the rows of a stacked batch take the stack's (%r)" % (dtype, stack_args["dtype"]))
+        return int(capacity), stack_args["dtype"] == "float32"
+    return int(capacity), dtype == "float32"
+
+
+class Terminal:
+    """What the auto-reset inside step() used to throw away (BatchedMiniWorld.terminal_enable; include/miniworld_batch.h at
+    mwb_terminal_enable): the frame every episode ended on, why it ended, and the stacked observation the policy would have seen -
+    the info["terminal_observation"] and info["TimeLimit.truncated"] of a modern VecEnv.  Zero-copy views, valid from the return
+    of a step() until the batch's next pass:
+        cause [N] uint8         END_CLOCK (1: step_count >= max_episode_steps) | END_TASK (2: a task rule), 0 = the episode goes on
+        frames [N, ...]         shaped like obs: frames[e] is env e's frame at `done` wherever done[e] (stale elsewhere)
+        grey [N, ...]           shaped like batch.grey (greyscale=True), else None
+        count [1] int32         how many envs ended in the last step (may exceed capacity)
+        row_of [N] int32        the compact row of env e's terminal observation, -1: it did not end, or count passed capacity
+        row_env [capacity]      the env of row r, -1 behind the rows written
+        rows [capacity, C * nstack, W, H]   the stacked terminal observations in the fused stack's dtype: the nstack - 1 frames
+                                before the terminal one (zeros where the episode was shorter), then the terminal frame; without a
+                                stack [capacity, ...] single frames shaped like obs, uint8 or float32
+    reset(), reset(mask), render() and copy_envs() produce none: after them count = 0, row_of = -1, cause = 0."""
+
+    def __init__(self, batch, capacity=None, dtype=None):
+        torch = batch.torch
+        self.batch, self.L, self.torch = batch, batch.L, torch
+        capacity, is_float = check_terminal_args(capacity, batch.num_envs, batch._ctor["auto_reset"], batch._stack_args, dtype)
+        _lib.check(self.L.mwb_terminal_enable(batch.h, capacity, _lib.TERMINAL_FLOAT if is_float and batch._stack_args is None else 0))
+        info = _lib.MwbTerminalInfo()
+        _lib.check(self.L.mwb_terminal_info(batch.h, ctypes.byref(info)))
+        N, W, H, K = batch.num_envs, batch.W, batch.H, int(info.capacity)
+        self.num_envs, self.capacity, self.nstack, self.channels = N, K, int(info.nstack), int(info.planes)
+        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, batch), device=batch.device)  # noqa: E731
+        hwc = batch.layout == "HWC"
+        self.cause = as_t(info.cause, (N,), "|u1")
+        self.frames = as_t(info.frames, (N, H, W, 3) if hwc else (N, 3, W, H), "|u1")
+        self.grey = as_t(info.grey, (N, H, W, 1) if hwc else (N, 1, W, H), "<f4") if info.grey else None
+        self.row_of, self.row_env, self.count = as_t(info.row_of, (N,), "<i4"), as_t(info.row_env, (K,), "<i4"), as_t(info.count, (1,), "<i4")
+        ts = "<f4" if info.rows_float else "|u1"
+        if batch._stack_args is not None:
+            self.rows = as_t(info.rows, (K, self.channels, W, H), ts)
+        else:
+            self.rows = as_t(info.rows, (K, H, W, 3) if hwc else (K, 3, W, H), ts)
+        self.nbytes = int(info.frames_bytes + info.grey_bytes + info.rows_bytes)
+
+    @property
+    def truncated(self):
+        """bool [N] on the device: the episode ended by the clock alone - the state is not terminal, bootstrap from it"""
+        return self.cause == _lib.END_CLOCK
+
+    @property
+    def terminated(self):
+        """bool [N] on the device: a task rule ended the episode (whatever the clock said)"""
+        return (self.cause & _lib.END_TASK) != 0
+
+    def dropped(self):
+        """Ended envs that got no row because more than `capacity` ended in one step, since the last call (synchronous)"""
+        n = ctypes.c_ulonglong()
+        _lib.check(self.L.mwb_terminal_dropped(self.batch.h, ctypes.byref(n)))
+        return int(n.value)
+
+
 class _DevView:
     """Exposes a library-owned device buffer through __cuda_array_interface__ (zero-copy)."""
 
@@ -503,6 +599,7 @@ class BatchedMiniWorld:
                           task_args=task_args, auto_reset=auto_reset, greyscale=greyscale)
         self._stack_args = None
         self.monitor = None   # monitor_enable()
+        self.terminal = None  # terminal_enable()
         self.torch = torch
         self.L = _lib.load()
         if task is None:
@@ -952,6 +1049,9 @@ class BatchedMiniWorld:
         torch = self.torch
         is_f = {"float32": 1, "uint8": 0}[dtype]
         sliding = sliding or fused
+        if self.terminal is not None:
+            raise ValueError("stack_enable: after terminal_enable (which lays its rows out for the stack it finds); a batch with "
+                             "terminal observations takes stack_enable(fused=True) before terminal_enable")
         _lib.check(self.L.mwb_stack_enable(self.h, int(nstack), is_f | (_lib.STACK_SLIDING if sliding else 0) | (_lib.STACK_FUSED if fused else 0) |
                                            (_lib.STACK_GREY if grey else 0)))
         out = _lib.MwbOutputs()
@@ -995,6 +1095,17 @@ class BatchedMiniWorld:
         mon = Monitor(self, capacity, quota_max)
         self.monitor = mon
         return mon
+
+    def terminal_enable(self, capacity=None, dtype=None):
+        """Terminal observations and the cause of every episode's end (mwb_terminal_enable): from now on step() / step_repeat()
+        render the frame of every env that ends BEFORE regenerating it and report why it ended.  capacity (None: num_envs): the
+        stacked rows kept per step; dtype ("uint8" / "float32"): of the rows of a batch without a frame stack (a stacked batch's
+        rows take the stack's).  Call before the first reset(), after stack_enable(fused=True) where a stack is used; a
+        non-fused stack is refused.  Returns the Terminal (also self.terminal)."""
+        if getattr(self, "terminal", None) is not None:
+            raise ValueError("terminal_enable: already enabled")
+        self.terminal = Terminal(self, capacity, dtype)
+        return self.terminal
 
     def frame_reuse_stats(self):
         """(frames reused, frames rendered) by the step passes since the last call (mwb_frame_reuse_stats; synchronous).  A step

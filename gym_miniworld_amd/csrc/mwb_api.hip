@@ -120,6 +120,10 @@ struct mwb_handle {
     void *monitor_mem = nullptr;
     void *monitor_pack = nullptr;       // last_return | last_len | last_calls | counts | logged | retired, contiguous
     size_t monitor_pack_bytes = 0;
+    // ---- terminal observations (mwb_terminal_enable): its buffers are in `allocs`; dev.end_cause is terminal.cause
+    bool terminal_on = false;
+    MwbTerminal terminal = {};
+    size_t terminal_rows_bytes = 0;
 };
 #define MWB_COPY_TABLE_DESCS 64
 static unsigned long long g_next_serial = 1;
@@ -612,6 +616,38 @@ static int stack_advance(mwb_handle *h, int after_reset, hipStream_t s) {
     return MWB_OK;
 }
 
+// Terminal observations (mwb_terminal_enable), immediately BEFORE the reset launch of a step: reset_list holds exactly the envs that
+// ended and their state is still the terminal state - reset_kernel destroys it, and render_kernel mode 1 zeroes the regenerated
+// envs' stack history.  Rank the ended envs, render their frames through the list path (prep mode 1 + render mode 1) with a copy of
+// the MwbDev whose outputs point at the terminal buffers, then write the compact stacked rows.  The copy redirects everything
+// mode 1 writes: obs, grey and the frame constants; depth, the fused stack, the workgroup time stamps and the last-frame cache are
+// off (mode 1 writes no `cost` and, with reuse_pass 0, no reuse statistics).  step_pass = 1: the frame is the step's own, the render
+// override (ovr_slot / ovr_pose) is honoured.  Tiled handles go through the same calls.
+static int terminal_pass(mwb_handle *h, hipStream_t s) {
+    if (!h->terminal_on) return MWB_OK;
+    const MwbTerminal &t = h->terminal;
+    mwb_launch_terminal_rank(t, h->dev.reset_set, s);
+    int rc = check_launch("terminal_rank_kernel"); if (rc) return rc;
+    MwbDev v = h->dev;
+    v.obs = t.frames; v.grey = t.grey_frames; v.frame = t.frame_consts;
+    v.depth = nullptr; v.want_depth = 0;
+    v.stk = nullptr; v.wg_ts = nullptr;
+    v.frame_cache = nullptr; v.depth_cache = nullptr; v.frame_cached = nullptr; v.frame_same = nullptr; v.reuse_pass = 0;
+    v.step_pass = 1;
+    mwb_launch_prep(v, 1, s);
+    rc = check_launch("prep_kernel"); if (rc) return rc;
+    mwb_launch_render(v, 1, s);
+    rc = check_launch("render_kernel"); if (rc) return rc;
+    mwb_launch_terminal_stack(t, h->stack, h->stack_planes, h->stack_pos, s);
+    return check_launch("terminal_stack_kernel");
+}
+// a pass that is not a step has no terminal observations: count = 0, no rows, no causes
+static int terminal_clear(mwb_handle *h, hipStream_t s) {
+    if (!h->terminal_on) return MWB_OK;
+    mwb_launch_terminal_clear(h->terminal, s);
+    return check_launch("terminal_clear_kernel");
+}
+
 static int ensure_ready(mwb_handle *h, bool renders = true) {   // the caller holds the device guard
     if (!h->seeded) return set_err(MWB_ESTATE, "mwb_seed must be called before reset/step (the reference seeds from entropy; this library refuses to)");
     if (h->textures_dirty || !h->have_textures) { int rc = upload_textures(h); if (rc) return rc; rc = invalidate_frames(h, 0, h->dev.N); if (rc) return rc; }
@@ -629,6 +665,7 @@ extern "C" int mwb_reset(mwb_handle *h, const uint8_t *mask_dev, void *stream) {
     h->dev.step_pass = 0; h->dev.reuse_pass = 0;   // every frame is rendered (and the last-frame cache refreshed)
     rc = timing_begin(h, s); if (rc) return rc;
     rc = stack_advance(h, mask_dev == nullptr, s); if (rc) return rc;   // a full reset restarts the window; a partial one is a step for the others
+    rc = terminal_clear(h, s); if (rc) return rc;
     mwb_launch_mark_reset(h->dev, mask_dev, s);
     rc = check_launch("mark_reset_kernel"); if (rc) return rc;
     TMARK(1); TMARK(5);
@@ -696,6 +733,7 @@ static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *s
     }
     TMARK(1);
     if (!h->overlap_reset) {
+        rc = terminal_pass(h, s); if (rc) return rc;
         TMARK(5);
         mwb_launch_reset(h->dev, 1024, s);
         rc = check_launch("reset_kernel"); if (rc) return rc;
@@ -708,6 +746,7 @@ static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *s
     // caller's stream renders everybody else; join before returning control of the outputs
     HIP_TRY(hipEventRecord(h->ev_fork, s));
     HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
+    rc = terminal_pass(h, h->side); if (rc) return rc;   // the ended envs' last frames, while their state is still there
     if (h->timing_now) HIP_TRY(hipEventRecord(h->ev[5], h->side));
     mwb_launch_reset(h->dev, 1024, h->side);   // a handful of envs end per step - or all of them (mass time-out); started ahead of the bulk render
     rc = check_launch("reset_kernel"); if (rc) return rc;
@@ -733,6 +772,7 @@ extern "C" int mwb_render(mwb_handle *h, void *stream) {
     h->dev.reuse_pass = 0;
     h->dev.step_pass = 0;   // the current state (render_obs() called again shows what the task rule left)
     rc = timing_begin(h, s); if (rc) return rc;
+    rc = terminal_clear(h, s); if (rc) return rc;
     TMARK(1); TMARK(5); TMARK(6); TMARK(2);
     return render_tail(h, 0, s);
 }
@@ -821,6 +861,7 @@ extern "C" int mwb_grey_enable(mwb_handle *h) {
     if (!h) return set_err(MWB_EINVAL, "mwb_grey_enable: null handle");
     MwbDev &d = h->dev;
     if (d.grey) return set_err(MWB_ESTATE, "mwb_grey_enable: already enabled");
+    if (h->terminal_on) return set_err(MWB_ESTATE, "mwb_grey_enable: enable greyscale before mwb_terminal_enable (it allocates the terminal grey frames)");
     if ((d.W * d.H) % 4) return set_err(MWB_EINVAL, "mwb_grey_enable: W*H must be a multiple of 4");
     if (d.tile_w > 0) return set_err(MWB_EINVAL, "mwb_grey_enable: not available when observations are rendered in tiles (large frames, MWB_TILE): use mwb_grey_convert");
     // the buffer is filled by the pass that writes obs: enabled after the first one it would lack the frame already rendered
@@ -865,6 +906,9 @@ extern "C" int mwb_stack_enable(mwb_handle *h, int nstack, int dtype) {
     if (d.layout != MWB_LAYOUT_CWH) return set_err(MWB_EINVAL, "mwb_stack_enable: the frame stack is channel-first, create the handle with MWB_LAYOUT_CWH");
     if ((d.W * d.H) % 4) return set_err(MWB_EINVAL, "mwb_stack_enable: W*H must be a multiple of 4");
     if (h->stack) return set_err(MWB_ESTATE, "mwb_stack_enable: already enabled");
+    // the terminal rows were laid out for the handle as mwb_terminal_enable found it; they are built from a fused window only
+    if (h->terminal_on) return set_err(MWB_ESTATE, fused ? "mwb_stack_enable: enable the frame stack before mwb_terminal_enable (the terminal rows are laid out by it)"
+                                                         : "mwb_stack_enable: a handle with mwb_terminal_enable takes the fused frame stack only (MWB_STACK_FUSED, enabled before it)");
     if (grey && dtype != 1) return set_err(MWB_EINVAL, "mwb_stack_enable: MWB_STACK_GREY needs dtype float32 (the reference defines no uint8 grey)");
     if (grey && !d.grey) return set_err(MWB_ESTATE, "mwb_stack_enable: MWB_STACK_GREY needs mwb_grey_enable first");
     // a fused window is filled by the render kernels as they produce frames: enabled after the first observation it would
@@ -1225,6 +1269,86 @@ extern "C" int mwb_rollout_gather_cols(mwb_handle *h, const int64_t *index_dev, 
     return check_launch("rollout_gather_cols_kernel");
 }
 
+// -------------------------------------------------------------------------------- terminal observations
+// the frame an episode ended on, why it ended, compact stacked rows; the arithmetic is mwb_terminal_map.h, the kernels
+// mwb_terminal.hip, the pass itself terminal_pass() above
+extern "C" int mwb_terminal_enable(mwb_handle *h, int capacity, unsigned flags) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_terminal_enable: null handle");
+    MwbDev &d = h->dev;
+    if (h->terminal_on) return set_err(MWB_ESTATE, "mwb_terminal_enable: already enabled");
+    if (!d.auto_reset) return set_err(MWB_EINVAL, "mwb_terminal_enable: the handle was created with no_auto_reset (its observation IS the terminal frame)");
+    if (capacity < 1 || capacity > d.N) return set_err(MWB_EINVAL, "mwb_terminal_enable: capacity must lie in 1 .. num_envs");
+    if (flags & ~(unsigned)MWB_TERMINAL_FLOAT) return set_err(MWB_EINVAL, "mwb_terminal_enable: unknown flag");
+    if (h->stack && !h->stack_fused)
+        return set_err(MWB_EINVAL, "mwb_terminal_enable: the handle's frame stack is not MWB_STACK_FUSED (the terminal rows are built from the fused window's history)");
+    if (h->stack && (flags & MWB_TERMINAL_FLOAT) && h->stack_dtype != 1)
+        return set_err(MWB_EINVAL, "mwb_terminal_enable: MWB_TERMINAL_FLOAT on a handle with a uint8 frame stack (the rows take the stack's dtype)");
+    // the terminal frame of the very first step needs the buffers: nothing may have been rendered yet
+    if (h->have_obs) return set_err(MWB_ESTATE, "mwb_terminal_enable: must be called before the first mwb_reset / mwb_step / mwb_render");
+    USE_DEVICE(h->cfg.device);
+    MwbTerminal t = {};
+    t.N = d.N; t.capacity = capacity; t.plane = (size_t)d.W * d.H;
+    t.nstack = h->stack ? h->stack_n : 1; t.cpf = h->stack ? h->stack_cpf : 3;
+    t.rows_float = h->stack ? h->stack_dtype == 1 : (flags & MWB_TERMINAL_FLOAT) != 0;
+    t.grey = h->stack && h->stack_cpf == 1;
+    const size_t N = (size_t)d.N, rows_bytes = (size_t)capacity * t.nstack * t.cpf * t.plane * (t.rows_float ? 4 : 1);
+    int rc = dev_alloc(h, &t.frames, N * t.plane * 3);
+    if (!rc && d.grey) rc = dev_alloc(h, &t.grey_frames, N * t.plane);
+    if (!rc) rc = dev_alloc(h, &t.frame_consts, N * d.frame_words);
+    if (!rc) rc = dev_alloc(h, &t.cause, N);
+    if (!rc) rc = dev_alloc(h, &t.row_of, N);
+    if (!rc) rc = dev_alloc(h, &t.row_env, (size_t)capacity);
+    if (!rc) rc = dev_alloc(h, &t.count, (size_t)1);
+    if (!rc) rc = dev_alloc(h, &t.dropped, (size_t)1);
+    if (!rc) rc = dev_alloc(h, &t.rows, rows_bytes);
+    if (rc) return rc;   // (what was allocated is freed with the handle)
+    HIP_TRY(hipMemset(t.row_of, 0xFF, N * sizeof(int32_t)));   // -1: no env has a row
+    HIP_TRY(hipMemset(t.row_env, 0xFF, (size_t)capacity * sizeof(int32_t)));
+    HIP_TRY(hipDeviceSynchronize());
+    h->terminal = t; h->terminal_rows_bytes = rows_bytes; h->terminal_on = true;
+    d.end_cause = t.cause;
+    return MWB_OK;
+}
+
+extern "C" int mwb_terminal_info(mwb_handle *h, struct mwb_terminal_info *out) {
+    if (!h || !out) return set_err(MWB_EINVAL, "mwb_terminal_info: null argument");
+    if (!h->terminal_on) return set_err(MWB_ESTATE, "mwb_terminal_info: call mwb_terminal_enable first");
+    const MwbTerminal &t = h->terminal;
+    memset(out, 0, sizeof(*out));
+    out->cause = t.cause; out->frames = t.frames; out->grey = t.grey_frames; out->row_of = t.row_of; out->row_env = t.row_env; out->count = t.count;
+    out->rows = t.rows;
+    out->frames_bytes = (size_t)t.N * t.plane * 3; out->grey_bytes = t.grey_frames ? (size_t)t.N * t.plane * sizeof(float) : 0;
+    out->rows_bytes = h->terminal_rows_bytes;
+    out->capacity = t.capacity; out->rows_float = t.rows_float; out->planes = t.nstack * t.cpf; out->nstack = t.nstack;
+    return MWB_OK;
+}
+
+extern "C" int mwb_terminal_dropped(mwb_handle *h, unsigned long long *envs) {
+    if (!h || !envs) return set_err(MWB_EINVAL, "mwb_terminal_dropped: null argument");
+    *envs = 0;
+    if (!h->terminal_on) return set_err(MWB_ESTATE, "mwb_terminal_dropped: call mwb_terminal_enable first");
+    USE_DEVICE(h->cfg.device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(envs, h->terminal.dropped, sizeof(*envs), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(h->terminal.dropped, 0, sizeof(*envs)));
+    HIP_TRY(hipDeviceSynchronize());
+    return MWB_OK;
+}
+
+extern "C" int mwb_rollout_bootstrap(mwb_handle *h, const float *value_rows_dev, double gamma, void *stream) {
+    if (!h || !value_rows_dev) return set_err(MWB_EINVAL, "mwb_rollout_bootstrap: null argument");
+    if (!h->terminal_on) return set_err(MWB_ESTATE, "mwb_rollout_bootstrap: call mwb_terminal_enable first");
+    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_bootstrap: call mwb_rollout_enable first");
+    const MwbRollout &r = h->rollout;
+    if (r.cursor < 1) return set_err(MWB_ESTATE, "mwb_rollout_bootstrap: no transition has been pushed in this window yet");
+    USE_DEVICE(h->cfg.device);
+    MwbReturnsTables tab;
+    mwb_returns_tables(gamma, 1.0, &tab);
+    const size_t at = (size_t)(r.cursor - 1) * r.N;
+    mwb_launch_terminal_bootstrap(h->terminal, tab, r.reward + at, h->learner_on ? h->learner.taken + at : nullptr, value_rows_dev, (hipStream_t)stream);
+    return check_launch("terminal_bootstrap_kernel");
+}
+
 // ------------------------------------------------------------------------------ copying environments
 // the first field of the two configurations that differs (num_envs and domain_rand may), or null.  Compared as the handles use
 // them: defaults filled in (max_episode_steps <= 0, task_args 0, use_default_params)
@@ -1297,6 +1421,7 @@ extern "C" int mwb_copy_envs(mwb_handle *dst, const int32_t *dst_idx_dev, mwb_ha
     if (render) { rc = ensure_ready(dst); if (rc) return rc; }   // MWB_ESTATE without seed / textures / meshes: what mwb_render needs
     hipStream_t s = (hipStream_t)stream;
     MwbDev &d = dst->dev;
+    rc = terminal_clear(dst, s); if (rc) return rc;   // a pass on dst that is no step
     if (!dst->copy_dst_pairs) { rc = dev_alloc(dst, &dst->copy_dst_pairs, (size_t)d.N); if (rc) return rc; }
     if (!dst->copy_src_mark) { rc = dev_alloc(dst, &dst->copy_src_mark, (size_t)d.N); if (rc) return rc; }
     if (!dst->copy_rejected) {

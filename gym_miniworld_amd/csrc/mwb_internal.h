@@ -241,6 +241,10 @@ struct MwbDev {
     // worlds step_kernel culls (mwb_step_culls): the segments once more, env-major, so that the few groups an env does load are
     // 256 contiguous bytes each - out of the transposed block a single lane's group is 32 lines, 4 KB of traffic.  Null otherwise
     double *seg_rows;       // [N][S_max][4]
+    // ---- mwb_terminal_enable (last on purpose, as frozen was).  Null otherwise.  Why the step ended env e's episode: MWB_END_CLOCK |
+    // MWB_END_TASK, 0 where it goes on (and for a skip-masked env); written by the step kernels where they write done.  An output
+    // of a pass, not state: not in the array list below, never copied
+    uint8_t *end_cause;     // [N]
 };
 // step_kernel culls by group where a wave (it has STEP_PARTS = 8) would otherwise walk a chain of batches: more than 64 segments
 MWB_SEG_HD static inline bool mwb_step_culls(int S_max) { return mwb_seg_groups(S_max) > 8; }
@@ -417,6 +421,30 @@ struct MwbMonitor {
 void mwb_launch_monitor_update(const MwbMonitor &m, const uint8_t *skip, const double *reward, const uint8_t *done, const int32_t *taken, hipStream_t s);
 void mwb_launch_monitor_clear(const MwbMonitor &m, const uint8_t *mask, int partial, hipStream_t s);
 void mwb_launch_monitor_quota(const MwbMonitor &m, int quota, hipStream_t s);
+
+// ---- terminal observations (mwb_terminal_enable; mwb_terminal_map.h says which row an ended env gets and where its history
+// lies in the fused stack).  Passed by value to the kernels of mwb_terminal.hip.  Terminal depth maps are not produced.
+struct MwbTerminal {
+    int N, capacity;
+    int nstack, cpf;          // frames per row and planes per frame: 1 / 3 without a stack, else the fused stack's
+    int rows_float, grey;     // rows are float32 (else uint8); the newest group comes from `grey` (a grey stack) instead of `frames`
+    size_t plane;             // W * H
+    uint8_t *frames;          // [N][plane * 3] the terminal frames, in the handle's layout
+    float *grey_frames;       // [N][plane] or null
+    float *frame_consts;      // [N][frame_words] the terminal render's own frame constants
+    uint8_t *cause;           // [N] = MwbDev::end_cause
+    int32_t *row_of, *row_env, *count;   // [N], [capacity], [1]
+    unsigned long long *dropped;         // [1] ended envs without a row since mwb_terminal_dropped last read it
+    char *rows;               // [capacity][nstack * cpf * plane] u8 or f32
+};
+// launch wrappers implemented in mwb_terminal.hip.  rank: row_of / row_env / count / dropped from reset_set; stack: the rows of the
+// envs rank listed - stk = the fused stack's base (null: no stack), stk_K planes per env, window at stk_pos; clear: count = 0,
+// row_of = row_env = -1, cause = 0; bootstrap: reward_t / taken_t = row t of the rollout's columns (taken_t null: k = 1)
+void mwb_launch_terminal_rank(const MwbTerminal &t, const uint8_t *reset_set, hipStream_t s);
+void mwb_launch_terminal_stack(const MwbTerminal &t, const void *stk, int stk_K, int stk_pos, hipStream_t s);
+void mwb_launch_terminal_clear(const MwbTerminal &t, hipStream_t s);
+void mwb_launch_terminal_bootstrap(const MwbTerminal &t, const MwbReturnsTables &tab, float *reward_t, const int32_t *taken_t, const float *value_rows,
+                                   hipStream_t s);
 
 // launch wrappers implemented in mwb_kernels.hip
 void mwb_launch_step(const MwbDev &d, const int32_t *actions, const uint8_t *skip_mask, hipStream_t s);   // entity tasks: step_ents_kernel

@@ -218,6 +218,7 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
         if (dummy) {
             d.reward[e] = -99.0f; d.reward64[e] = -99.0; d.done[e] = 0; d.ep_steps[e] = d.step_count[e];
             d.reset_set[e] = 0;
+            if (d.end_cause) d.end_cause[e] = 0;
             d.feature[e * 2] = 0.0f; d.feature[e * 2 + 1] = 0.0f;   // info = {"feature": [0, 0]}
             if (d.frame_same) d.frame_same[e] = d.frame_cached[e];   // not stepped: the frame on record is the frame
         }
@@ -461,8 +462,8 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
     }
     d.carrying[e] = carried;
     double r = 0.0;
-    int done = 0;
-    if (sc >= d.max_episode_steps) { done = 1; r = 0.0; }   // miniworld.py:708-711
+    int done = 0;   // raised by the task rule; the clock's is kept apart and ORed in below (d.end_cause tells them apart)
+    const int clock_done = sc >= d.max_episode_steps;   // miniworld.py:708-711 (its `reward = 0` is r's initial value)
     {   // near(box), miniworld.py:961-971, then the task rule (e.g. envs/maze.py:106-113)
         const double max_forward_step = max_fwd;
         bool near[NBX];
@@ -497,6 +498,8 @@ __global__ void __launch_bounds__(64 * STEP_PARTS) step_kernel(MwbDev d, const i
             if (d.task == MWB_TASK_TMAZE || d.task == MWB_TASK_YMAZE) { d.goal_pos[e * 3] = bx[0]; d.goal_pos[e * 3 + 1] = 0.0; d.goal_pos[e * 3 + 2] = bz[0]; }
         }
     }
+    if (d.end_cause) d.end_cause[e] = (uint8_t)((clock_done ? MWB_END_CLOCK : 0) | (done ? MWB_END_TASK : 0));
+    done |= clock_done;
     d.reward64[e] = r; d.reward[e] = (float)r; d.done[e] = (uint8_t)done; d.ep_steps[e] = sc;
     const bool regen = done && d.auto_reset;   // worker auto-reset, vec_env/subproc_vec_env.py:10-13
     d.reset_set[e] = (uint8_t)regen;
@@ -523,6 +526,7 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
         // not stepped: the frame on record is the frame - unless it still shows the entity an override put back for the step before
         if (d.frame_same) d.frame_same[e] = (uint8_t)(d.ovr_slot[e] < 0 && d.frame_cached[e]);
         d.reset_set[e] = 0; d.ovr_slot[e] = -1;
+        if (d.end_cause) d.end_cause[e] = 0;
         d.feature[e * 2] = 0.0f; d.feature[e * 2 + 1] = 0.0f;
         return;
     }
@@ -629,8 +633,8 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
     }
     // ---- obs = self.render_obs() happens here in the reference; the task rules follow
     double r = 0.0;
-    int done = 0;
-    if (sc >= d.max_episode_steps) { done = 1; r = 0.0; }   // miniworld.py:708-711
+    int done = 0;   // raised by the task rule; the clock's is kept apart and ORed in below (d.end_cause tells them apart)
+    const int clock_done = sc >= d.max_episode_steps;   // miniworld.py:708-711 (its `reward = 0` is r's initial value)
     auto near = [&](int slot) {   // MiniWorldEnv.near(ent), miniworld.py:961-971
         const size_t be = (size_t)slot * N + e;
         const double ddx = d.box_x[be] - ax, ddy = d.box_y[be] - 0.0, ddz = d.box_z[be] - az;
@@ -707,6 +711,8 @@ __global__ void __launch_bounds__(64) step_ents_kernel(MwbDev d, const int32_t *
     d.carrying[e] = carried;
     d.n_order[e] = n_ord;
     d.feature[e * 2] = feat0; d.feature[e * 2 + 1] = 0.0f;
+    if (d.end_cause) d.end_cause[e] = (uint8_t)((clock_done ? MWB_END_CLOCK : 0) | (done ? MWB_END_TASK : 0));
+    done |= clock_done;
     d.reward64[e] = r; d.reward[e] = (float)r; d.done[e] = (uint8_t)done; d.ep_steps[e] = sc;
     const bool regen = done && d.auto_reset;
     d.reset_set[e] = (uint8_t)regen;

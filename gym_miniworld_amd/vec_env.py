@@ -81,12 +81,19 @@ class LazyInfos:
     steps of the episode that ended last in every env, and episode_logged bool [N], the envs whose episode ended - and was logged -
     in this step: for those info['episode'] = {'r', 'l', 't'} as the reference's bench.Monitor wrapper delivers it (main.py:262;
     from memory, parity unpinned: the wrapper belongs to the un-vendored `baselines` and rounds r and t to 6 places - nothing is
-    rounded here).  An env whose episode's start the monitor did not see (a copy_envs destination) carries no 'episode'."""
+    rounded here).  An env whose episode's start the monitor did not see (a copy_envs destination) carries no 'episode'.
+    With terminal observations (MiniWorldVecEnv(terminal_obs=K)): truncated and terminated bool [N] - the episode ended in this
+    step by the clock alone / by a task rule - and terminal_row int [N], the row of envs.terminal.rows that holds the env's
+    terminal observation (-1: none).  An env that ended carries info['TimeLimit.truncated'] (True only for a clock-only end) and,
+    where it has a row, info['terminal_observation'] = terminal_obs[row]: a device tensor, valid until the next step."""
 
     def __init__(self, n, goal_pos=None, feature=None, skipped=None, default_feature=False, health=None, taken=None,
-                 episode_r=None, episode_l=None, episode_logged=None, episode_t=0.0):
+                 episode_r=None, episode_l=None, episode_logged=None, episode_t=0.0, truncated=None, terminated=None,
+                 terminal_row=None, terminal_obs=None, terminal_index=None):
         self.n, self.goal_pos, self.skipped = n, goal_pos, skipped
         self.taken = taken
+        self.truncated, self.terminated, self.terminal_row, self.terminal_obs = truncated, terminated, terminal_row, terminal_obs
+        self._terminal_index = terminal_row if terminal_index is None else terminal_index   # where terminal_obs is not indexed by row
         self.episode_r, self.episode_l, self.episode_logged, self.episode_t = episode_r, episode_l, episode_logged, episode_t
         self.health = health   # CollectHealth: info['health'] (collecthealth.py:75), float64 [N] or None
         self._task_feature = feature is not None
@@ -107,6 +114,10 @@ class LazyInfos:
         info = {}
         if self.episode_logged is not None and self.episode_logged[i]:
             info["episode"] = {"r": float(self.episode_r[i]), "l": int(self.episode_l[i]), "t": self.episode_t}
+        if self.truncated is not None and (self.truncated[i] or self.terminated[i]):   # the episode ended in this step
+            info["TimeLimit.truncated"] = bool(self.truncated[i])
+            if self.terminal_obs is not None and self._terminal_index[i] >= 0:
+                info["terminal_observation"] = self.terminal_obs[int(self._terminal_index[i])]
         if self.goal_pos is not None:
             info["goal_pos"] = self.goal_pos[i].copy()
         if self.health is not None:
@@ -121,6 +132,17 @@ class LazyInfos:
 
     def __iter__(self):
         return (self[i] for i in range(self.n))
+
+
+def terminal_infos(cause, capacity):
+    """The terminal part of a step's infos from the cause bytes alone (uint8 [N] on the host): (truncated, terminated,
+    terminal_row).  The rows are the device's (csrc/mwb_terminal_map.h): the envs that ended, in ascending env index, take rows
+    0, 1, ..; from `capacity` on they have none (-1)."""
+    cause = np.asarray(cause, dtype=np.uint8)
+    ended = cause != 0
+    rank = np.cumsum(ended) - 1
+    row = np.where(ended & (rank < int(capacity)), rank, -1).astype(np.int64)
+    return cause == 1, (cause & 2) != 0, row
 
 
 class MiniWorldVecEnv(VecEnv):
@@ -154,6 +176,13 @@ class MiniWorldVecEnv(VecEnv):
                        step (part of the captured graph with graph=True); envs.monitor.stats() is what the trainer prints.  An env
                        whose episode ended carries info['episode'] = {'r', 'l', 't'}; monitor_quota_max=Q (0 .. 64, default 8) sizes
                        the per-env evaluation table: the most episodes per env evaluate() can be asked for
+    terminal_obs=K  -> what the auto-reset inside step() throws away (BatchedMiniWorld.terminal_enable): `envs.terminal` holds the
+                       frame every episode ended on, the cause of its end and up to K stacked terminal observations per step (True:
+                       one per env).  An env that ended carries info['TimeLimit.truncated'] - True only where the clock alone
+                       ended the episode - and info['terminal_observation'], a device tensor in the form of one observation
+                       (valid until the next step); infos.truncated / terminated / terminal_row for the whole batch.  With
+                       rollout_steps: envs.rollout.bootstrap_truncated(V(envs.terminal.rows), gamma) after the step.  Not with
+                       graph=True (that path keeps the non-fused stack)
     feature_info    -> every info dict carries "feature" (length-2 zeros) as the fork's PPO loop
                        requires (pytorch-a2c-ppo-acktr/main.py:614-619)
     graph=True      -> after two eager steps the whole step (mwb_step's kernels on both streams, the frame-stack /
@@ -168,12 +197,17 @@ class MiniWorldVecEnv(VecEnv):
 
     def __init__(self, env_id, num_envs, seed=1, device=0, domain_rand=False, transpose=True, to_float=True,
                  frame_stack=0, torch_api=True, feature_info=False, first_env_index=0, graph=False, greyscale=False, frame_skip=1,
-                 rollout_steps=0, rollout_learner=False, monitor=0, monitor_quota_max=8, **kwargs):
+                 rollout_steps=0, rollout_learner=False, monitor=0, monitor_quota_max=8, terminal_obs=0, **kwargs):
         import torch
-        from .batch import BatchedMiniWorld
+        from .batch import BatchedMiniWorld, check_terminal_args
         from . import _lib
         self.torch = torch
         self.greyscale = bool(greyscale)
+        if terminal_obs and graph:
+            raise ValueError("terminal_obs cannot be combined with graph=True: the captured step keeps the non-fused frame stack, "
+                             "the terminal rows are built from the fused one")
+        if terminal_obs:   # True: a row for every env; checked before anything is created
+            terminal_obs = check_terminal_args(None if terminal_obs is True else terminal_obs, num_envs, kwargs.get("auto_reset", True))[0]
         if rollout_steps and graph:
             raise ValueError("rollout_steps cannot be combined with graph=True: the rollout's cursor and ring position live on the "
                              "host, a replayed graph would freeze them")
@@ -205,6 +239,14 @@ class MiniWorldVecEnv(VecEnv):
                     raise
                 # observations rendered in tiles (frames too large for one workgroup's LDS, MWB_TILE): the sliding window, one pass
                 self.stackedobs = b.stack_enable(self.nstack, "float32" if to_float else "uint8", sliding=not graph, fused=False)
+        # terminal observations: after the stack (its rows are laid out for it), before anything renders.  Their form is the
+        # observation's: the stacked rows, single RGB frames in the observation's dtype, or - greyscale without a stack - the
+        # terminal grey frames themselves, which are indexed by env
+        self.terminal = b.terminal_enable(terminal_obs, dtype=None if self.nstack else ("float32" if to_float else "uint8")) if terminal_obs else None
+        self._term_obs, self._term_by_env = None, False
+        if self.terminal is not None:
+            self._term_by_env = self.greyscale and not self.nstack
+            self._term_obs = self.terminal.grey if self._term_by_env else self.terminal.rows
         # the trainer's RolloutStorage on the device: pushed by reset() and by the device part of every step
         self.rollout = b.rollout_enable(int(rollout_steps), nstack=self.nstack or 1, grey=self.greyscale,
                                         learner=bool(rollout_learner)) if rollout_steps else None
@@ -235,6 +277,10 @@ class MiniWorldVecEnv(VecEnv):
         self._h_feat = part("feature", np.float32, 2 * n).reshape(n, 2) if (b.has_features or b.has_health) else None
         self._h_skip = pin((num_envs,), torch.uint8)
         self._h_taken = pin((num_envs,), torch.int32) if self.frame_skip > 1 else None   # filled by a copy of its own, beside the pack's
+        self._h_cause = pin((num_envs,), torch.uint8) if self.terminal is not None else None   # one more small copy beside the pack's
+        self._term_none = (np.zeros(num_envs, bool), np.zeros(num_envs, bool), np.full(num_envs, -1, np.int64))
+        for arr in self._term_none:
+            arr.setflags(write=False)
         self._h_mon = None   # the monitor's host pack: one more copy beside the pack's
         if self.monitor is not None:
             mo = self.monitor.host_pack_offsets
@@ -292,6 +338,8 @@ class MiniWorldVecEnv(VecEnv):
             self._h_mon.copy_(self.monitor.host_pack, non_blocking=True)
         if self._h_taken is not None:
             self._h_taken.copy_(b.taken, non_blocking=True)   # same stream, ahead of step_wait's one wait
+        if self._h_cause is not None:
+            self._h_cause.copy_(self.terminal.cause, non_blocking=True)
         return obs
 
     def step_async(self, actions, mask=None):
@@ -354,6 +402,14 @@ class MiniWorldVecEnv(VecEnv):
         if self._h_mon is not None:   # info['episode'] of the envs whose episode ended, and was logged, in this step
             ep = dict(episode_r=self._h_ep_r.copy(), episode_l=self._h_ep_l.copy(), episode_logged=self._h_ep_logged.astype(bool) & dones,
                       episode_t=time.time() - self._t0)
+        if self._h_cause is not None:   # why the episodes ended, and where their terminal observations are
+            if dones.any():
+                trunc, term, row = terminal_infos(self._h_cause.numpy(), self.terminal.capacity)
+            else:   # most steps of a large batch: nothing ended, nothing to derive (read-only constants)
+                trunc, term, row = self._term_none
+            ep.update(truncated=trunc, terminated=term, terminal_row=row, terminal_obs=self._term_obs)
+            if self._term_by_env:   # (the grey frames are indexed by env, and every env that ended has one)
+                ep.update(terminal_index=np.where(trunc | term, np.arange(self.num_envs), -1))
         if b.has_health:   # CollectHealth: info['health'] (delivered in feature[:, 0])
             infos = LazyInfos(self.num_envs, health=self._h_feat[:, 0].astype(np.float64), skipped=sk, default_feature=self.feature_info, taken=tk, **ep)
         elif b.has_goal_pos:   # the T-maze family: info['goal_pos'] (tmaze.py:66,206) and, where produced, info['feature']

@@ -578,6 +578,58 @@ struct mwb_monitor_counts {
 };
 int mwb_monitor_read(mwb_handle *h, struct mwb_monitor_counts *out);   /* synchronous */
 
+/* ---- terminal observations and the cause of an episode's end ---------------------------------------- */
+/* replaces: what the reference's VecEnv worker throws away when it resets a finished env inside step
+ * (vec_env/subproc_vec_env.py:10-13: `if done: ob = env.reset()` overwrites the frame step() rendered at `done`), and what a
+ * modern VecEnv reports instead: info["terminal_observation"] and info["TimeLimit.truncated"].  MiniWorldEnv.step ends an episode
+ * for two reasons that `done` merges (miniworld.py:708-711: `if self.step_count >= self.max_episode_steps: done = True`, and the
+ * task's own rule on top); the reward cannot tell them apart.
+ *
+ * Opt-in: a handle that never calls mwb_terminal_enable launches exactly what it launched before.  On an enabled handle every
+ * mwb_step / mwb_step_i64 / mwb_step_repeat
+ *   - writes cause[e] = MWB_END_CLOCK | MWB_END_TASK bits where the step kernels write done[e]: 0 = the episode goes on (also for
+ *     a skip-masked env); under mwb_step_repeat the byte of the env's last sub-step;
+ *   - BEFORE it regenerates the envs that ended, renders their terminal frame - the step's own frame, as the observation of a
+ *     no_auto_reset handle shows it (PickupObjs: the object picked up last is still drawn) - into frames[e] (and grey[e] on a
+ *     handle with mwb_grey_enable), ranks them in ascending env index (row_of[e] = rank or -1, row_env[r] = env, count[0] = how
+ *     many ended, possibly more than `capacity`) and writes for each of the first `capacity` of them one compact row: the
+ *     stacked observation the policy would have seen had the env not been reset - the nstack - 1 history groups of the fused
+ *     stack's window followed by the terminal frame - or, without a stack, the single frame.
+ * Ended envs beyond `capacity` get no row (row_of = -1) and are counted; their frames[e] is still written.  All of it is ordered
+ * before the step returns control of its outputs and stays valid until the handle's next pass.  mwb_reset, mwb_render and
+ * mwb_copy_envs into the handle launch no terminal pass: after them count = 0, row_of = -1 and cause = 0 everywhere.
+ * Terminal depth maps are not produced.
+ *
+ * mwb_terminal_enable: the handle auto-resets, 1 <= capacity <= num_envs, flags 0 or MWB_TERMINAL_FLOAT (stack-less handles: rows
+ * are float32 instead of uint8; with a stack the rows take the stack's dtype), called before the first pass and AFTER
+ * mwb_grey_enable / mwb_stack_enable where the handle uses them (it lays the rows out for the handle as it finds it; either call
+ * is refused afterwards).  A handle with a frame stack must have the fused one (MWB_STACK_FUSED): a non-fused stack is refused
+ * here, and mwb_stack_enable of one is refused after this call.  A grey fused stack gives grey rows.  MWB_EINVAL / MWB_ESTATE
+ * otherwise, and nothing changes. */
+#define MWB_END_CLOCK 1   /* step_count >= max_episode_steps */
+#define MWB_END_TASK 2    /* a task rule raised done */
+#define MWB_TERMINAL_FLOAT 1
+int mwb_terminal_enable(mwb_handle *h, int capacity, unsigned flags);
+/* the device arrays (fixed for the handle's lifetime).  Tag only, as struct mwb_rollout_info */
+struct mwb_terminal_info {
+    uint8_t *cause;                   /* u8 [N] */
+    uint8_t *frames;                  /* u8 [N][W*H*3] in the handle's layout, env-indexed */
+    float *grey;                      /* f32 [N][W*H] or NULL */
+    int32_t *row_of, *row_env, *count;   /* i32 [N], [capacity], [1] */
+    void *rows;                       /* [capacity][row_elems], u8 or f32 */
+    size_t frames_bytes, grey_bytes, rows_bytes;
+    int32_t capacity, rows_float, planes, nstack;   /* planes per row: C * nstack (3 or 1 per frame) */
+};
+int mwb_terminal_info(mwb_handle *h, struct mwb_terminal_info *out);   /* MWB_ESTATE before mwb_terminal_enable */
+int mwb_terminal_dropped(mwb_handle *h, unsigned long long *envs);     /* synchronous; reads and clears */
+/* The standard time-limit bootstrap on the rollout storage: for every terminal row r of the last step whose env e = row_env[r]
+ * ended by the clock alone (cause[e] == MWB_END_CLOCK), reward[t][e] += G[k] * value_rows_dev[r] at t = cursor - 1, the transition
+ * pushed last: one float32 multiply, then one float32 add.  G[k] = (float)(gamma^k) is the table of mwb_rollout_returns, k =
+ * taken[t][e] with the learner half, 1 without.  value_rows_dev: f32 [capacity], V(rows[r]).  Envs without a row are skipped (they
+ * are counted in mwb_terminal_dropped).  MWB_ESTATE unless both mwb_terminal_enable and mwb_rollout_enable were called and the
+ * cursor is at least 1. */
+int mwb_rollout_bootstrap(mwb_handle *h, const float *value_rows_dev, double gamma, void *stream);
+
 /* World generation cannot fail for the four tasks with sane arguments; if it ever does (a portal outside
  * its wall, more than one portal on an edge, a placement that finds no free spot in 100000 draws - the
  * reference would assert or spin) the kernel flags it. Synchronous: returns MWB_ESTATE if any env of the
