@@ -35,6 +35,9 @@ RETURNS_DISCOUNTED, RETURNS_GAE, RETURNS_PSI = 0, 1, 2   # MWB_RETURNS_*
 MONITOR_MAX_CAPACITY, MONITOR_MAX_QUOTA = 65536, 64      # csrc/mwb_monitor_map.h
 END_CLOCK, END_TASK = 1, 2   # MWB_END_*: the bits of the terminal pass's `cause`
 TERMINAL_FLOAT = 1           # MWB_TERMINAL_FLOAT
+LEVELS_SEQUENTIAL, LEVELS_UNIFORM, LEVELS_TABLE = 0, 1, 2   # MWB_LEVELS_*: how a level set hands out levels
+LEVELS_TALLY = 1             # MWB_LEVELS_TALLY
+LEVELS_MAX, LEVELS_MAX_TABLE, LEVELS_MAX_TALLY = 2 ** 31 - 1, 2 ** 24, 2 ** 22   # csrc/mwb_levels_map.h
 
 
 class MwbConfig(ctypes.Structure):
@@ -96,6 +99,12 @@ class MwbTerminalInfo(ctypes.Structure):   # struct mwb_terminal_info
                [(n, ctypes.c_int32) for n in ("capacity", "rows_float", "planes", "nstack")]
 
 
+class MwbLevelsInfo(ctypes.Structure):   # struct mwb_levels_info
+    _fields_ = [(n, ctypes.c_void_p) for n in ("index", "prev_index", "next_level", "episode_no", "tallies", "level_seeds")] + \
+               [("num_levels", ctypes.c_int64), ("start_level", ctypes.c_uint64), ("sampler_seed", ctypes.c_uint64),
+                ("env_offset", ctypes.c_int64), ("env_stride", ctypes.c_int64), ("mode", ctypes.c_int32), ("flags", ctypes.c_uint32)]
+
+
 class MwbMonitorCounts(ctypes.Structure):   # struct mwb_monitor_counts, as it lies on the device
     _fields_ = [("total", ctypes.c_ulonglong), ("dropped", ctypes.c_ulonglong), ("remaining", ctypes.c_uint32), ("quota", ctypes.c_uint32),
                 ("last_base", ctypes.c_uint32), ("last_count", ctypes.c_uint32)]
@@ -115,6 +124,7 @@ EXPORTS = [
     "mwb_bulk_variant",
     "mwb_monitor_enable", "mwb_monitor_update", "mwb_monitor_clear", "mwb_monitor_quota", "mwb_monitor_info", "mwb_monitor_read",
     "mwb_terminal_enable", "mwb_terminal_info", "mwb_terminal_dropped", "mwb_rollout_bootstrap",
+    "mwb_levels_enable", "mwb_levels_restart", "mwb_levels_info", "mwb_levels_rejected",
 ]
 
 _lib = None
@@ -202,6 +212,11 @@ def load():
         L.mwb_terminal_info.argtypes = [vp, ctypes.POINTER(MwbTerminalInfo)]
         L.mwb_terminal_dropped.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
         L.mwb_rollout_bootstrap.argtypes = [vp, vp, ctypes.c_double, vp]
+    if hasattr(L, "mwb_levels_enable"):   # (an older library through MWB_LIB, scripts/bench_levels.py's parent leg)
+        L.mwb_levels_enable.argtypes = [vp, ctypes.c_int64, ctypes.c_uint64, vp, i32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint]
+        L.mwb_levels_restart.argtypes = [vp, i32, ctypes.c_uint64, i32, vp]
+        L.mwb_levels_info.argtypes = [vp, ctypes.POINTER(MwbLevelsInfo)]
+        L.mwb_levels_rejected.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
     if hasattr(L, "mwb_bulk_variant"):   # (an older library loaded through MWB_LIB for a kernel A/B has none; build() checks EXPORTS)
         L.mwb_bulk_variant.argtypes = [vp]
     L.mwb_timing_read.argtypes = [vp] +[ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(i32)]

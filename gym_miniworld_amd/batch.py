@@ -571,6 +571,149 @@ class Terminal:
         return int(n.value)
 
 
+LEVEL_MODES = {"sequential": _lib.LEVELS_SEQUENTIAL, "uniform": _lib.LEVELS_UNIFORM, "table": _lib.LEVELS_TABLE}
+_M64 = (1 << 64) - 1
+_GOLD = 0x9E3779B97F4A7C15
+
+
+def _mix64(z):
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def level_of(mode, g, n, L, stride=1, sampler_seed=0, request=-1):
+    """The level of assignment n of the env with global index g in a set of L levels - csrc/mwb_levels_map.h restated with Python
+    integers, for tests and for users who want to know ahead of time what an env will play.  mode: "sequential" ((g + n * stride)
+    mod L), "uniform" (two rounds of splitmix64's mix over sampler_seed, g and n, then the high word of h * L), or "table" (the
+    request where 0 <= request < L, the uniform level otherwise)."""
+    mode = LEVEL_MODES[mode] if isinstance(mode, str) else int(mode)
+    g, n, L = int(g), int(n), int(L)
+    if mode == _lib.LEVELS_SEQUENTIAL:
+        return (g + n * int(stride)) % L
+    if mode == _lib.LEVELS_TABLE and 0 <= int(request) < L:
+        return int(request)
+    a = _mix64((int(sampler_seed) + _GOLD * (g + 1)) & _M64)
+    h = _mix64((a + _GOLD * (n + 1)) & _M64)
+    return (h * L) >> 64
+
+
+def check_levels_args(num_levels, start_level=0, seeds=None, mode="uniform", sampler_seed=0, tally=True, env_stride=None, num_envs=1):
+    """What levels_enable refuses before anything is created (mwb_levels_enable would answer MWB_EINVAL): raises ValueError for a
+    num_levels that is no integer in 1 .. 2^31 - 1, a seed table of another length or of more than 2^24 levels, seeds or a start
+    level outside uint64, an unknown mode, a stride below 1, tallies beyond 2^22 levels.  Returns (num_levels, start_level, seeds as
+    a uint64 array or None, mode number, sampler_seed, tally, env_stride)."""
+    def integer(x, what):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise ValueError("levels_enable: %s must be an integer, not %r" % (what, x))
+        return int(x)
+    L = integer(num_levels, "num_levels")
+    if not 1 <= L <= _lib.LEVELS_MAX:
+        raise ValueError("levels_enable: num_levels %d outside 1 .. 2^31 - 1" % L)
+    start = integer(start_level, "start_level")
+    sampler_seed = integer(sampler_seed, "sampler_seed")
+    for what, x in (("start_level", start), ("sampler_seed", sampler_seed)):
+        if not 0 <= x <= _M64:
+            raise ValueError("levels_enable: %s %d outside uint64" % (what, x))
+    if isinstance(mode, str) and mode in LEVEL_MODES:
+        mode = LEVEL_MODES[mode]
+    elif isinstance(mode, bool) or mode not in LEVEL_MODES.values():
+        raise ValueError("levels_enable: mode must be one of %s, not %r" % (sorted(LEVEL_MODES), mode))
+    table = None
+    if seeds is not None:
+        vals = [integer(x, "every seed") for x in (seeds.tolist() if isinstance(seeds, np.ndarray) else list(seeds))]
+        if len(vals) != L:
+            raise ValueError("levels_enable: %d seeds for num_levels = %d" % (len(vals), L))
+        if L > _lib.LEVELS_MAX_TABLE:
+            raise ValueError("levels_enable: a seed table holds at most 2^24 levels")
+        if any(not 0 <= x <= _M64 for x in vals):
+            raise ValueError("levels_enable: seeds outside uint64")
+        table = np.array(vals, dtype=np.uint64)
+    stride = max(1, int(num_envs)) if env_stride is None else integer(env_stride, "env_stride")
+    if stride < 1:
+        raise ValueError("levels_enable: env_stride %d < 1" % stride)
+    if tally and L > _lib.LEVELS_MAX_TALLY:
+        raise ValueError("levels_enable: tally=True takes at most 2^22 levels (num_levels = %d)" % L)
+    return L, start, table, int(mode), sampler_seed, bool(tally), stride
+
+
+class Levels:
+    """A level set (BatchedMiniWorld.levels_enable; include/miniworld_batch.h at mwb_levels_enable): Procgen's num_levels /
+    start_level for this batch.  Every regeneration of an env - the auto-reset inside step(), reset(mask), reset() - starts from the
+    generator stream of a level seed chosen on the device, so the episode equals the first episode of a reference env after
+    env.seed(level_seed); env.reset().  Zero-copy device views:
+        index [N] int32        the level every env is in (-1 before its first assignment, or after a copy from a batch without levels)
+        prev_index [N] int32   the level of its previous episode (-1: none)
+        episode_no [N] int64   assignments since enable / restart()
+        next_level [N] int32   mode "table": write the level an env is to play next; consumed (set to -1) when it is taken
+        episodes, steps, successes [L] int64   with tally=True: per level, the episodes that ended in a step(), their env steps and
+                               how many ended with a reward > 0 (the sparse-reward tasks' success; it means little for PickupObjs
+                               and CollectHealth); None otherwise.  reset() abandons episodes and tallies nothing.
+    The T-maze family's episode_count / task_step_count / goal_idx carry on across a regeneration, as across env.seed()."""
+
+    def __init__(self, batch, args, env_offset):
+        torch = batch.torch
+        self.batch, self.L = batch, batch.L
+        self.num_levels, self.start_level, self._seeds, self._mode, self._sampler_seed, self.tally, self.env_stride = args
+        self.env_offset = int(env_offset)
+        _lib.check(self.L.mwb_levels_enable(batch.h, self.num_levels, self.start_level,
+                                            self._seeds.ctypes.data_as(ctypes.c_void_p) if self._seeds is not None else None, self._mode,
+                                            self._sampler_seed, self.env_offset, self.env_stride, _lib.LEVELS_TALLY if self.tally else 0))
+        info = _lib.MwbLevelsInfo()
+        _lib.check(self.L.mwb_levels_info(batch.h, ctypes.byref(info)))
+        N, nl = batch.num_envs, self.num_levels
+        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, batch), device=batch.device)  # noqa: E731
+        self.index, self.prev_index = as_t(info.index, (N,), "<i4"), as_t(info.prev_index, (N,), "<i4")
+        self.next_level, self.episode_no = as_t(info.next_level, (N,), "<i4"), as_t(info.episode_no, (N,), "<i8")
+        self.index_pair = as_t(info.index, (2, N), "<i4")   # index | prev_index are one allocation: a VecEnv's host mirror is one copy
+        assert info.prev_index == info.index + 4 * N
+        self.episodes = self.steps = self.successes = None
+        if info.tallies:   # (counts stay far below 2^63: int64 views of the uint64 words)
+            t = as_t(info.tallies, (3, nl), "<i8")
+            self.episodes, self.steps, self.successes = t[0], t[1], t[2]
+
+    @property
+    def mode(self):
+        return {v: k for k, v in LEVEL_MODES.items()}[self._mode]
+
+    @property
+    def sampler_seed(self):
+        return self._sampler_seed
+
+    def params(self):
+        """the keyword arguments that enable the same set on another batch (archive())"""
+        return dict(num_levels=self.num_levels, start_level=self.start_level, seeds=self._seeds, mode=self._mode,
+                    sampler_seed=self._sampler_seed, tally=self.tally, env_stride=self.env_stride)
+
+    def restart(self, mode=None, sampler_seed=None, clear_tally=True):
+        """episode_no = 0 for every env - the sequence of levels starts over - and, with clear_tally, zero tallies; mode and
+        sampler_seed change where given.  A small kernel on the current stream; index and prev_index stay."""
+        args = check_levels_args(1, 0, None, self._mode if mode is None else mode, self._sampler_seed if sampler_seed is None else sampler_seed, False, 1)
+        _lib.check(self.L.mwb_levels_restart(self.batch.h, args[3], args[4], 1 if clear_tally else 0, self.batch._stream()))
+        self._mode, self._sampler_seed = args[3], args[4]
+
+    def rejected(self):
+        """next_level entries other than -1 that were out of range since the last call (synchronous)"""
+        n = ctypes.c_ulonglong()
+        _lib.check(self.L.mwb_levels_rejected(self.batch.h, ctypes.byref(n)))
+        return int(n.value)
+
+    def seed_of(self, index):
+        """level index (an int, or an array of them) -> its seed as a Python int (a list of them); -1 -> None.  Host arithmetic."""
+        def one(i):
+            i = int(i)
+            if i < 0:
+                return None
+            if i >= self.num_levels:
+                raise IndexError("level %d of %d" % (i, self.num_levels))
+            return int(self._seeds[i]) if self._seeds is not None else (self.start_level + i) & _M64
+        return one(index) if np.isscalar(index) else [one(i) for i in np.asarray(index).reshape(-1).tolist()]
+
+    def level_of(self, env, n):
+        """the level env `env` of this batch takes at its n-th assignment under the current mode (no request)"""
+        return level_of(self._mode, self.env_offset + int(env), n, self.num_levels, self.env_stride, self._sampler_seed)
+
+
 class _DevView:
     """Exposes a library-owned device buffer through __cuda_array_interface__ (zero-copy)."""
 
@@ -600,6 +743,7 @@ class BatchedMiniWorld:
         self._stack_args = None
         self.monitor = None   # monitor_enable()
         self.terminal = None  # terminal_enable()
+        self.levels = None    # levels_enable()
         self.torch = torch
         self.L = _lib.load()
         if task is None:
@@ -903,10 +1047,13 @@ class BatchedMiniWorld:
 
     def archive(self, capacity):
         """A sibling batch of `capacity` slots with this batch's constructor arguments (and its frame stack, if one is enabled):
-        unseeded, never reset or rendered, without textures or meshes - a place to save() env states to and restore() them from."""
+        unseeded, never reset or rendered, without textures or meshes - a place to save() env states to and restore() them from.  The
+        archive of a batch with level sets has the same set (without tallies), so that save / restore keep an env's level index."""
         a = BatchedMiniWorld(num_envs=int(capacity), seed=None, _assets=False, **self._ctor)
         if self._stack_args is not None:
             a.stack_enable(**self._stack_args)
+        if self.levels is not None:   # save / restore keep the level index (an archive never steps: it needs no tallies)
+            a.levels_enable(**dict(self.levels.params(), tally=False))
         return a
 
     def save(self, archive, slots, envs):
@@ -1106,6 +1253,19 @@ class BatchedMiniWorld:
             raise ValueError("terminal_enable: already enabled")
         self.terminal = Terminal(self, capacity, dtype)
         return self.terminal
+
+    def levels_enable(self, num_levels, start_level=0, seeds=None, mode="uniform", sampler_seed=0, tally=True, env_stride=None):
+        """Level sets (mwb_levels_enable; Procgen's num_levels / start_level): from now on every regeneration of an env starts
+        from the generator stream of a level seed chosen on the device - seeds[i] where a table of num_levels seeds is given,
+        start_level + i otherwise.  mode: "sequential" (env g plays (g + n * env_stride) mod num_levels in its n-th episode),
+        "uniform" (a hash of sampler_seed, g and n) or "table" (levels.next_level, uniform where it holds none); g =
+        first_env_index + e, env_stride defaults to num_envs.  tally: per-level episode / step / success counts (num_levels <=
+        2^22).  The batch needs no seed() afterwards.  Once per batch; returns the Levels (also self.levels)."""
+        if getattr(self, "levels", None) is not None:
+            raise ValueError("levels_enable: already enabled")
+        args = check_levels_args(num_levels, start_level, seeds, mode, sampler_seed, tally, env_stride, self.num_envs)
+        self.levels = Levels(self, args, self.first_env_index)
+        return self.levels
 
     def frame_reuse_stats(self):
         """(frames reused, frames rendered) by the step passes since the last call (mwb_frame_reuse_stats; synchronous).  A step

@@ -18,12 +18,16 @@
 #include "mwb_lds_layout.h"
 #include "mwb_rollout_map.h"
 #include "mwb_monitor_map.h"
+#include "mwb_levels_map.h"
 #include "mwb_returns_scan.h"
 #include "mwb_task_table.h"
 #include "mwb_texture_host.h"
 
 static_assert(mwb_task_frame_words(1) == MWB_FRAME_WORDS_FOR(1) && mwb_task_frame_words(MWB_MAX_ENTS) == MWB_FRAME_WORDS_FOR(MWB_MAX_ENTS),
               "mwb_task_table.h restates the frame constants' size");
+
+static_assert(MWB_LEVELS_SEQUENTIAL == MWB_LEVELS_MODE_SEQUENTIAL && MWB_LEVELS_UNIFORM == MWB_LEVELS_MODE_UNIFORM && MWB_LEVELS_TABLE == MWB_LEVELS_MODE_TABLE,
+              "mwb_levels_map.h restates the level modes");
 
 static thread_local std::string g_err;
 static int set_err(int code, const std::string &msg) { g_err = msg; return code; }
@@ -124,6 +128,12 @@ struct mwb_handle {
     bool terminal_on = false;
     MwbTerminal terminal = {};
     size_t terminal_rows_bytes = 0;
+    // ---- level sets (mwb_levels_enable): its buffers are in `allocs`; mode and sampler seed as the host set them last
+    bool levels_on = false;
+    MwbLevels levels = {};
+    int levels_mode = 0;
+    uint64_t levels_sampler_seed = 0;
+    unsigned levels_flags = 0;
 };
 #define MWB_COPY_TABLE_DESCS 64
 static unsigned long long g_next_serial = 1;
@@ -131,97 +141,12 @@ static unsigned long long g_next_serial = 1;
 extern "C" const char *mwb_last_error(void) { return g_err.c_str(); }
 extern "C" int mwb_abi_version(void) { return MWB_ABI_VERSION; }
 
-// ------------------------------------------------------------------------------------ SHA-512
-// Needed for the seed -> MT19937 key mapping of gym<=0.21 (gym/utils/seeding.py hash_seed, an
-// un-vendored dependency of reference random.py:10): key = little-endian 32-bit limbs of the first
-// 8 bytes of sha512(str(seed)).  "Parity unpinned": gym is not available to check against.
-static const uint64_t K512[80] = {
-    0x428a2f98d728ae22ULL, 0x7137449123ef65cdULL, 0xb5c0fbcfec4d3b2fULL, 0xe9b5dba58189dbbcULL, 0x3956c25bf348b538ULL,
-    0x59f111f1b605d019ULL, 0x923f82a4af194f9bULL, 0xab1c5ed5da6d8118ULL, 0xd807aa98a3030242ULL, 0x12835b0145706fbeULL,
-    0x243185be4ee4b28cULL, 0x550c7dc3d5ffb4e2ULL, 0x72be5d74f27b896fULL, 0x80deb1fe3b1696b1ULL, 0x9bdc06a725c71235ULL,
-    0xc19bf174cf692694ULL, 0xe49b69c19ef14ad2ULL, 0xefbe4786384f25e3ULL, 0x0fc19dc68b8cd5b5ULL, 0x240ca1cc77ac9c65ULL,
-    0x2de92c6f592b0275ULL, 0x4a7484aa6ea6e483ULL, 0x5cb0a9dcbd41fbd4ULL, 0x76f988da831153b5ULL, 0x983e5152ee66dfabULL,
-    0xa831c66d2db43210ULL, 0xb00327c898fb213fULL, 0xbf597fc7beef0ee4ULL, 0xc6e00bf33da88fc2ULL, 0xd5a79147930aa725ULL,
-    0x06ca6351e003826fULL, 0x142929670a0e6e70ULL, 0x27b70a8546d22ffcULL, 0x2e1b21385c26c926ULL, 0x4d2c6dfc5ac42aedULL,
-    0x53380d139d95b3dfULL, 0x650a73548baf63deULL, 0x766a0abb3c77b2a8ULL, 0x81c2c92e47edaee6ULL, 0x92722c851482353bULL,
-    0xa2bfe8a14cf10364ULL, 0xa81a664bbc423001ULL, 0xc24b8b70d0f89791ULL, 0xc76c51a30654be30ULL, 0xd192e819d6ef5218ULL,
-    0xd69906245565a910ULL, 0xf40e35855771202aULL, 0x106aa07032bbd1b8ULL, 0x19a4c116b8d2d0c8ULL, 0x1e376c085141ab53ULL,
-    0x2748774cdf8eeb99ULL, 0x34b0bcb5e19b48a8ULL, 0x391c0cb3c5c95a63ULL, 0x4ed8aa4ae3418acbULL, 0x5b9cca4f7763e373ULL,
-    0x682e6ff3d6b2b8a3ULL, 0x748f82ee5defb2fcULL, 0x78a5636f43172f60ULL, 0x84c87814a1f0ab72ULL, 0x8cc702081a6439ecULL,
-    0x90befffa23631e28ULL, 0xa4506cebde82bde9ULL, 0xbef9a3f7b2c67915ULL, 0xc67178f2e372532bULL, 0xca273eceea26619cULL,
-    0xd186b8c721c0c207ULL, 0xeada7dd6cde0eb1eULL, 0xf57d4f7fee6ed178ULL, 0x06f067aa72176fbaULL, 0x0a637dc5a2c898a6ULL,
-    0x113f9804bef90daeULL, 0x1b710b35131c471bULL, 0x28db77f523047d84ULL, 0x32caab7b40c72493ULL, 0x3c9ebe0a15c9bebcULL,
-    0x431d67c49c100d4cULL, 0x4cc5d4becb3e42b6ULL, 0x597f299cfc657e2aULL, 0x5fcb6fab3ad6faecULL, 0x6c44198c4a475817ULL};
-
-static inline uint64_t rotr64(uint64_t x, int n) { return (x >> n) | (x << (64 - n)); }
-
-static void sha512_short(const uint8_t *msg, size_t len, uint8_t out[64]) {   // len < 112: one block
-    uint8_t blk[128];
-    memset(blk, 0, sizeof(blk));
-    memcpy(blk, msg, len);
-    blk[len] = 0x80;
-    uint64_t bits = (uint64_t)len * 8;
-    for (int i = 0; i < 8; i++) blk[127 - i] = (uint8_t)(bits >> (8 * i));
-    uint64_t Hs[8] = {0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL, 0xa54ff53a5f1d36f1ULL,
-                      0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL, 0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
-    uint64_t w[80];
-    for (int i = 0; i < 16; i++) {
-        w[i] = 0;
-        for (int k = 0; k < 8; k++) w[i] = (w[i] << 8) | blk[i * 8 + k];
-    }
-    for (int i = 16; i < 80; i++) {
-        uint64_t s0 = rotr64(w[i - 15], 1) ^ rotr64(w[i - 15], 8) ^ (w[i - 15] >> 7);
-        uint64_t s1 = rotr64(w[i - 2], 19) ^ rotr64(w[i - 2], 61) ^ (w[i - 2] >> 6);
-        w[i] = w[i - 16] + s0 + w[i - 7] + s1;
-    }
-    uint64_t a = Hs[0], b = Hs[1], c = Hs[2], d = Hs[3], e = Hs[4], f = Hs[5], g = Hs[6], h = Hs[7];
-    for (int i = 0; i < 80; i++) {
-        uint64_t S1 = rotr64(e, 14) ^ rotr64(e, 18) ^ rotr64(e, 41);
-        uint64_t ch = (e & f) ^ (~e & g);
-        uint64_t t1 = h + S1 + ch + K512[i] + w[i];
-        uint64_t S0 = rotr64(a, 28) ^ rotr64(a, 34) ^ rotr64(a, 39);
-        uint64_t maj = (a & b) ^ (a & c) ^ (b & c);
-        uint64_t t2 = S0 + maj;
-        h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
-    }
-    Hs[0] += a; Hs[1] += b; Hs[2] += c; Hs[3] += d; Hs[4] += e; Hs[5] += f; Hs[6] += g; Hs[7] += h;
-    for (int i = 0; i < 8; i++)
-        for (int k = 0; k < 8; k++) out[i * 8 + k] = (uint8_t)(Hs[i] >> (56 - 8 * k));
-}
-
-// seed (already reduced mod 2^64 by the uint64 type) -> MT19937 init_by_array key
-static int seed_to_key(uint64_t seed, uint32_t key[2]) {
-    char txt[32];
-    int n = snprintf(txt, sizeof(txt), "%llu", (unsigned long long)seed);
-    uint8_t dig[64];
-    sha512_short((const uint8_t *)txt, (size_t)n, dig);
-    uint32_t lo = dig[0] | (dig[1] << 8) | (dig[2] << 16) | ((uint32_t)dig[3] << 24);
-    uint32_t hi = dig[4] | (dig[5] << 8) | (dig[6] << 16) | ((uint32_t)dig[7] << 24);
-    key[0] = lo; key[1] = hi;
-    return hi != 0 ? 2 : 1;   // _int_list_from_bigint drops the high limb when it is zero ([0] for 0)
-}
-
-extern "C" int mwb_seed_key(uint64_t seed, uint32_t key[2]) { return seed_to_key(seed, key); }
-
-// numpy RandomState.seed(list) == MT19937 init_by_array
-static void mt_init_by_array(uint32_t *mt, const uint32_t *init_key, int key_length) {
-    mt[0] = 19650218u;
-    for (int i = 1; i < 624; i++) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
-    int i = 1, j = 0;
-    for (int k = (624 > key_length ? 624 : key_length); k; k--) {
-        mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1664525u)) + init_key[j] + (uint32_t)j;
-        i++; j++;
-        if (i >= 624) { mt[0] = mt[623]; i = 1; }
-        if (j >= key_length) j = 0;
-    }
-    for (int k = 623; k; k--) {
-        mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1566083941u)) - (uint32_t)i;
-        i++;
-        if (i >= 624) { mt[0] = mt[623]; i = 1; }
-    }
-    mt[0] = 0x80000000u;
-    mt[624] = 624;   // position: the first draw regenerates the state
-}
+// ------------------------------------------------------------------------------------ seeds
+// The seed -> MT19937 state mapping of gym<=0.21 (gym/utils/seeding.py hash_seed, an un-vendored dependency of reference
+// random.py:10): key = little-endian 32-bit limbs of the first 8 bytes of sha512(str(seed)), then numpy's RandomState.seed(list) ==
+// init_by_array.  "Parity unpinned": gym is not available to check against.  The arithmetic is mwb_levels_map.h's - the functions
+// levels_assign_kernel runs on the device; there is no second copy here.
+extern "C" int mwb_seed_key(uint64_t seed, uint32_t key[2]) { return mwb_levels_seed_key(seed, key); }
 
 // ------------------------------------------------------------------------------------ helpers
 template <typename T>
@@ -556,10 +481,13 @@ extern "C" int mwb_seed(mwb_handle *h, const uint64_t *seeds) {
     if (!h || !seeds) return set_err(MWB_EINVAL, "mwb_seed: null argument");
     USE_DEVICE(h->cfg.device);
     std::vector<uint32_t> st((size_t)h->dev.N * MWB_MT_WORDS);
+    uint32_t base[624];
+    mwb_levels_mt_base(base);
     for (int e = 0; e < h->dev.N; e++) {
         uint32_t key[2];
-        int n = seed_to_key(seeds[e], key);
-        mt_init_by_array(&st[(size_t)e * MWB_MT_WORDS], key, n);
+        const int n = mwb_levels_seed_key(seeds[e], key);
+        MwbLevelsPlainRow row = {&st[(size_t)e * MWB_MT_WORDS]};
+        mwb_levels_init_by_array(row, base, key[0], key[1], n);
     }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h->dev.rng, st.data(), st.size() * 4, hipMemcpyHostToDevice));
@@ -648,6 +576,15 @@ static int terminal_clear(mwb_handle *h, hipStream_t s) {
     return check_launch("terminal_clear_kernel");
 }
 
+// Level sets (mwb_levels_enable), immediately before a reset launch: every env on reset_list gets its level and, in place of the
+// stream its last episode left, the generator row of the level's seed.  tally: the pass is a step (the listed envs ended an episode)
+static int levels_pass(mwb_handle *h, int tally, hipStream_t s) {
+    if (!h->levels_on) return MWB_OK;
+    const MwbDev &d = h->dev;
+    mwb_launch_levels_assign(h->levels, d.reset_list, d.reset_count, d.rng, d.done, d.reward64, d.ep_steps, tally, s);
+    return check_launch("levels_assign_kernel");
+}
+
 static int ensure_ready(mwb_handle *h, bool renders = true) {   // the caller holds the device guard
     if (!h->seeded) return set_err(MWB_ESTATE, "mwb_seed must be called before reset/step (the reference seeds from entropy; this library refuses to)");
     if (h->textures_dirty || !h->have_textures) { int rc = upload_textures(h); if (rc) return rc; rc = invalidate_frames(h, 0, h->dev.N); if (rc) return rc; }
@@ -668,6 +605,7 @@ extern "C" int mwb_reset(mwb_handle *h, const uint8_t *mask_dev, void *stream) {
     rc = terminal_clear(h, s); if (rc) return rc;
     mwb_launch_mark_reset(h->dev, mask_dev, s);
     rc = check_launch("mark_reset_kernel"); if (rc) return rc;
+    rc = levels_pass(h, 0, s); if (rc) return rc;   // a reset abandons episodes: nothing is tallied
     TMARK(1); TMARK(5);
     mwb_launch_reset(h->dev, MWB_RESET_MAX_BLOCKS, s);   // possibly every env: many blocks
     rc = check_launch("reset_kernel"); if (rc) return rc;
@@ -734,6 +672,7 @@ static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *s
     TMARK(1);
     if (!h->overlap_reset) {
         rc = terminal_pass(h, s); if (rc) return rc;
+        rc = levels_pass(h, 1, s); if (rc) return rc;
         TMARK(5);
         mwb_launch_reset(h->dev, 1024, s);
         rc = check_launch("reset_kernel"); if (rc) return rc;
@@ -747,6 +686,7 @@ static int step_impl(mwb_handle *h, const int32_t *actions_dev, const uint8_t *s
     HIP_TRY(hipEventRecord(h->ev_fork, s));
     HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
     rc = terminal_pass(h, h->side); if (rc) return rc;   // the ended envs' last frames, while their state is still there
+    rc = levels_pass(h, 1, h->side); if (rc) return rc;   // ... and their next level's generator rows, ahead of reset_kernel
     if (h->timing_now) HIP_TRY(hipEventRecord(h->ev[5], h->side));
     mwb_launch_reset(h->dev, 1024, h->side);   // a handful of envs end per step - or all of them (mass time-out); started ahead of the bulk render
     rc = check_launch("reset_kernel"); if (rc) return rc;
@@ -1349,6 +1289,86 @@ extern "C" int mwb_rollout_bootstrap(mwb_handle *h, const float *value_rows_dev,
     return check_launch("terminal_bootstrap_kernel");
 }
 
+// -------------------------------------------------------------------------------- level sets
+// every regeneration of an env starts from the generator row of a level seed chosen on the device; the arithmetic is
+// mwb_levels_map.h, the kernels mwb_levels.hip, the pass itself levels_pass() above
+extern "C" int mwb_levels_enable(mwb_handle *h, int64_t num_levels, uint64_t start_level, const uint64_t *level_seeds_host, int mode,
+                                 uint64_t sampler_seed, int64_t env_offset, int64_t env_stride, unsigned flags) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_levels_enable: null handle");
+    if (h->levels_on) return set_err(MWB_ESTATE, "mwb_levels_enable: already enabled");
+    if (num_levels < 1 || num_levels > MWB_LEVELS_MAX) return set_err(MWB_EINVAL, "mwb_levels_enable: num_levels must lie in 1 .. 2^31 - 1");
+    if (level_seeds_host && num_levels > MWB_LEVELS_MAX_TABLE) return set_err(MWB_EINVAL, "mwb_levels_enable: a seed table holds at most 2^24 levels");
+    if (mode != MWB_LEVELS_SEQUENTIAL && mode != MWB_LEVELS_UNIFORM && mode != MWB_LEVELS_TABLE) return set_err(MWB_EINVAL, "mwb_levels_enable: unknown mode");
+    if (env_offset < 0) return set_err(MWB_EINVAL, "mwb_levels_enable: env_offset < 0");
+    if (env_stride < 1) return set_err(MWB_EINVAL, "mwb_levels_enable: env_stride < 1");
+    if (flags & ~(unsigned)MWB_LEVELS_TALLY) return set_err(MWB_EINVAL, "mwb_levels_enable: unknown flag");
+    if ((flags & MWB_LEVELS_TALLY) && num_levels > MWB_LEVELS_MAX_TALLY) return set_err(MWB_EINVAL, "mwb_levels_enable: MWB_LEVELS_TALLY takes at most 2^22 levels");
+    USE_DEVICE(h->cfg.device);
+    MwbLevels v = {};
+    v.N = h->dev.N; v.L = num_levels; v.start_level = start_level; v.env_offset = env_offset; v.env_stride = env_stride;
+    const size_t N = (size_t)v.N, L = (size_t)num_levels;
+    uint64_t *seeds = nullptr; uint32_t *base = nullptr;
+    int rc = dev_alloc(h, &base, (size_t)624);
+    if (!rc && level_seeds_host) rc = dev_alloc(h, &seeds, L);
+    if (!rc) rc = dev_alloc(h, &v.params, (size_t)2);
+    if (!rc) rc = dev_alloc(h, &v.index, 2 * N);   // index | prev_index, contiguous: one copy mirrors both
+    if (!rc) rc = dev_alloc(h, &v.next_level, N);
+    if (!rc) rc = dev_alloc(h, &v.episode_no, N);
+    if (!rc) rc = dev_alloc(h, &v.rejected, (size_t)1);
+    if (!rc && (flags & MWB_LEVELS_TALLY)) rc = dev_alloc(h, &v.tallies, 3 * L);
+    if (rc) return rc;   // (what was allocated is freed with the handle)
+    uint32_t base_host[624];
+    mwb_levels_mt_base(base_host);   // the constant first loop of init_by_array: once, here
+    const uint64_t params[2] = {(uint64_t)mode, sampler_seed};
+    HIP_TRY(hipMemcpy(base, base_host, sizeof(base_host), hipMemcpyHostToDevice));
+    if (seeds) HIP_TRY(hipMemcpy(seeds, level_seeds_host, L * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v.params, params, sizeof(params), hipMemcpyHostToDevice));
+    v.prev_index = v.index + N;
+    HIP_TRY(hipMemset(v.index, 0xFF, 2 * N * sizeof(int32_t)));    // -1: no level yet, no previous one
+    HIP_TRY(hipMemset(v.next_level, 0xFF, N * sizeof(int32_t)));   // -1: no request
+    HIP_TRY(hipDeviceSynchronize());
+    v.base = base; v.seeds = seeds;
+    h->levels = v; h->levels_mode = mode; h->levels_sampler_seed = sampler_seed; h->levels_flags = flags; h->levels_on = true;
+    h->seeded = true;   // every env is given a stream before it is generated
+    return invalidate_frames(h, 0, h->dev.N);
+}
+
+extern "C" int mwb_levels_restart(mwb_handle *h, int mode, uint64_t sampler_seed, int clear_tally, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_levels_restart: null handle");
+    if (!h->levels_on) return set_err(MWB_ESTATE, "mwb_levels_restart: call mwb_levels_enable first");
+    if (mode != MWB_LEVELS_SEQUENTIAL && mode != MWB_LEVELS_UNIFORM && mode != MWB_LEVELS_TABLE) return set_err(MWB_EINVAL, "mwb_levels_restart: unknown mode");
+    USE_DEVICE(h->cfg.device);
+    mwb_launch_levels_restart(h->levels, mode, sampler_seed, clear_tally != 0, (hipStream_t)stream);
+    int rc = check_launch("levels_restart_kernel"); if (rc) return rc;
+    h->levels_mode = mode; h->levels_sampler_seed = sampler_seed;
+    return MWB_OK;
+}
+
+extern "C" int mwb_levels_info(mwb_handle *h, struct mwb_levels_info *out) {
+    if (!h || !out) return set_err(MWB_EINVAL, "mwb_levels_info: null argument");
+    if (!h->levels_on) return set_err(MWB_ESTATE, "mwb_levels_info: call mwb_levels_enable first");
+    const MwbLevels &v = h->levels;
+    memset(out, 0, sizeof(*out));
+    out->index = v.index; out->prev_index = v.prev_index; out->next_level = v.next_level; out->episode_no = v.episode_no;
+    out->tallies = v.tallies; out->level_seeds = v.seeds;
+    out->num_levels = v.L; out->start_level = v.start_level; out->sampler_seed = h->levels_sampler_seed;
+    out->env_offset = v.env_offset; out->env_stride = v.env_stride;
+    out->mode = h->levels_mode; out->flags = h->levels_flags;
+    return MWB_OK;
+}
+
+extern "C" int mwb_levels_rejected(mwb_handle *h, unsigned long long *entries) {
+    if (!h || !entries) return set_err(MWB_EINVAL, "mwb_levels_rejected: null argument");
+    *entries = 0;
+    if (!h->levels_on) return set_err(MWB_ESTATE, "mwb_levels_rejected: call mwb_levels_enable first");
+    USE_DEVICE(h->cfg.device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(entries, h->levels.rejected, sizeof(*entries), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset(h->levels.rejected, 0, sizeof(*entries)));
+    HIP_TRY(hipDeviceSynchronize());
+    return MWB_OK;
+}
+
 // ------------------------------------------------------------------------------ copying environments
 // the first field of the two configurations that differs (num_envs and domain_rand may), or null.  Compared as the handles use
 // them: defaults filled in (max_episode_steps <= 0, task_args 0, use_default_params)
@@ -1445,6 +1465,10 @@ extern "C" int mwb_copy_envs(mwb_handle *dst, const int32_t *dst_idx_dev, mwb_ha
     mwb_launch_copy_seg_box(d, dst->copy_pairs, count, s);
     rc = check_launch("copy_seg_box_kernel"); if (rc) return rc;
     dst->have_world = true;
+    if (dst->levels_on) {   // the level goes with the world: the source's index, or -1 (unknown) where the source has no level sets
+        mwb_launch_levels_copy(dst->levels.index, src->levels_on ? src->levels.index : nullptr, dst->copy_pairs, count, s);
+        rc = check_launch("levels_copy_kernel"); if (rc) return rc;
+    }
     if (render) {   // the destinations through the compact-list path, as mwb_render draws them: the current state, every frame rendered
         d.step_pass = 0; d.reuse_pass = 0;
         dst->timing_now = false;

@@ -446,6 +446,30 @@ void mwb_launch_terminal_clear(const MwbTerminal &t, hipStream_t s);
 void mwb_launch_terminal_bootstrap(const MwbTerminal &t, const MwbReturnsTables &tab, float *reward_t, const int32_t *taken_t, const float *value_rows,
                                    hipStream_t s);
 
+// ---- level sets (mwb_levels_enable; mwb_levels_map.h says which level an env takes and what its generator row becomes).  Passed
+// by value to the kernels of mwb_levels.hip; every buffer is the handle's own allocation.  MwbDev knows nothing of it: the kernels
+// take the arrays of MwbDev they touch as plain pointers.
+struct MwbLevels {
+    int N;
+    int64_t L;                       // levels of the set, 1 .. 2^31 - 1
+    uint64_t start_level;            // level i has the seed start_level + i ...
+    const uint64_t *seeds;           // ... unless a table was given: [L], else null
+    int64_t env_offset, env_stride;  // g = env_offset + e; SEQUENTIAL's stride
+    const uint32_t *base;            // [624] init_genrand(19650218), built once on the host
+    uint64_t *params;                // [2] mode, sampler_seed: device memory, so that a pass depends on no host state
+    int32_t *index, *prev_index, *next_level;   // [N] each
+    int64_t *episode_no;             // [N]
+    unsigned long long *rejected;    // [1] TABLE requests out of range since mwb_levels_rejected last read it
+    unsigned long long *tallies;     // [3][L] episodes, env steps, successes per level, or null
+};
+// launch wrappers implemented in mwb_levels.hip.  assign: every env of reset_list gets its level and its generator row (tally != 0:
+// the level it leaves is tallied first, from done / reward64 / ep_steps); restart: episode_no = 0, optionally the tallies, mode
+// and sampler seed; copy: index of the validated pairs {dst, src} (src_index null: the destinations' index becomes -1)
+void mwb_launch_levels_assign(const MwbLevels &v, const int32_t *reset_list, const int32_t *reset_count, uint32_t *rng, const uint8_t *done,
+                              const double *reward64, const int32_t *ep_steps, int tally, hipStream_t s);
+void mwb_launch_levels_restart(const MwbLevels &v, int mode, uint64_t sampler_seed, int clear_tally, hipStream_t s);
+void mwb_launch_levels_copy(int32_t *dst_index, const int32_t *src_index, const int2 *pairs, int count, hipStream_t s);
+
 // launch wrappers implemented in mwb_kernels.hip
 void mwb_launch_step(const MwbDev &d, const int32_t *actions, const uint8_t *skip_mask, hipStream_t s);   // entity tasks: step_ents_kernel
 void mwb_launch_clear_list(const MwbDev &d, hipStream_t s);

@@ -26,6 +26,14 @@ def shard_range(total_envs, rank, world_size):
     return first, count
 
 
+def shard_view_kwargs(total_envs, rank, world_size):
+    """(count, keyword arguments) for the MiniWorldVecEnv / make_vec_envs view of `rank`'s shard: its first env index - env i keeps
+    seed `base + i` and, with level sets (num_levels=L), its global index g - and the total env count as the level stride, so that
+    the levels an env plays ("sequential": (g + n * total_envs) mod L) do not depend on the sharding either."""
+    first, count = shard_range(total_envs, rank, world_size)
+    return count, dict(first_env_index=first, level_stride=int(total_envs))
+
+
 AUX_WORDS = 8   # float64 words per env in the small pack: reward, done, ep_steps, feature[2], goal_pos[3]
 
 

@@ -85,22 +85,44 @@ class LazyInfos:
     With terminal observations (MiniWorldVecEnv(terminal_obs=K)): truncated and terminated bool [N] - the episode ended in this
     step by the clock alone / by a task rule - and terminal_row int [N], the row of envs.terminal.rows that holds the env's
     terminal observation (-1: none).  An env that ended carries info['TimeLimit.truncated'] (True only for a clock-only end) and,
-    where it has a row, info['terminal_observation'] = terminal_obs[row]: a device tensor, valid until the next step."""
+    where it has a row, info['terminal_observation'] = terminal_obs[row]: a device tensor, valid until the next step.
+    With level sets (MiniWorldVecEnv(num_levels=L)): level and prev_level int32 [N], the level every env is in after this step and
+    the level of its previous episode (-1: none), and level_seed / prev_level_seed uint64 [N], their seeds (0 where the level is
+    -1; derived on first use, a step that nobody asks pays nothing for them).  Every info dict carries info['level_seed'] and,
+    where the env's episode ended in this step, info['prev_level_seed'] - Procgen's two keys, as Python ints (None for an unknown
+    level)."""
 
     def __init__(self, n, goal_pos=None, feature=None, skipped=None, default_feature=False, health=None, taken=None,
                  episode_r=None, episode_l=None, episode_logged=None, episode_t=0.0, truncated=None, terminated=None,
-                 terminal_row=None, terminal_obs=None, terminal_index=None):
+                 terminal_row=None, terminal_obs=None, terminal_index=None, level=None, prev_level=None, level_done=None,
+                 level_start=0, level_table=None):
         self.n, self.goal_pos, self.skipped = n, goal_pos, skipped
         self.taken = taken
         self.truncated, self.terminated, self.terminal_row, self.terminal_obs = truncated, terminated, terminal_row, terminal_obs
         self._terminal_index = terminal_row if terminal_index is None else terminal_index   # where terminal_obs is not indexed by row
         self.episode_r, self.episode_l, self.episode_logged, self.episode_t = episode_r, episode_l, episode_logged, episode_t
+        self.level, self.prev_level, self._level_done, self._level_start, self._level_table = level, prev_level, level_done, level_start, level_table
+        self._level_seeds = None
         self.health = health   # CollectHealth: info['health'] (collecthealth.py:75), float64 [N] or None
         self._task_feature = feature is not None
         self.feature = feature if feature is not None else (np.zeros((n, 2)) if default_feature else None)
 
     def __len__(self):
         return self.n
+
+    def _seeds(self):
+        if self._level_seeds is None:
+            self._level_seeds = (level_seeds_of(self.level, self._level_start, self._level_table),
+                                 level_seeds_of(self.prev_level, self._level_start, self._level_table))
+        return self._level_seeds
+
+    @property
+    def level_seed(self):
+        return None if self.level is None else self._seeds()[0]
+
+    @property
+    def prev_level_seed(self):
+        return None if self.level is None else self._seeds()[1]
 
     def __getitem__(self, i):
         if isinstance(i, slice):
@@ -118,6 +140,10 @@ class LazyInfos:
             info["TimeLimit.truncated"] = bool(self.truncated[i])
             if self.terminal_obs is not None and self._terminal_index[i] >= 0:
                 info["terminal_observation"] = self.terminal_obs[int(self._terminal_index[i])]
+        if self.level is not None:
+            info["level_seed"] = int(self.level_seed[i]) if self.level[i] >= 0 else None
+            if self._level_done is not None and self._level_done[i]:
+                info["prev_level_seed"] = int(self.prev_level_seed[i]) if self.prev_level[i] >= 0 else None
         if self.goal_pos is not None:
             info["goal_pos"] = self.goal_pos[i].copy()
         if self.health is not None:
@@ -143,6 +169,25 @@ def terminal_infos(cause, capacity):
     rank = np.cumsum(ended) - 1
     row = np.where(ended & (rank < int(capacity)), rank, -1).astype(np.int64)
     return cause == 1, (cause & 2) != 0, row
+
+
+def level_seeds_of(idx, start_level=0, seeds=None):
+    """level indices (int array) -> their seeds, uint64: seeds[i] where a table was given, start_level + i (uint64 arithmetic, as
+    the device's) otherwise; 0 for an unknown level (-1)"""
+    idx = np.asarray(idx)
+    known = idx >= 0
+    at = np.where(known, idx, 0).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        out = np.asarray(seeds, dtype=np.uint64)[at.astype(np.int64)] if seeds is not None else at + np.uint64(int(start_level))
+    return np.where(known, out, np.uint64(0)).astype(np.uint64)
+
+
+def level_infos(pair, dones, start_level=0, seeds=None):
+    """The level part of a step's infos from the host mirror of index | prev_index (int32 [2, N]) and the step's dones: the
+    keyword arguments LazyInfos takes - one copy of the mirror; the seeds are derived when somebody asks (level_seeds_of).  An
+    unknown level (-1) has no seed (0 in the arrays, None in the dicts)."""
+    pair = np.array(pair, dtype=np.int32)   # a copy: the mirror is overwritten by the next step
+    return dict(level=pair[0], prev_level=pair[1], level_done=dones, level_start=start_level, level_table=seeds)
 
 
 class MiniWorldVecEnv(VecEnv):
@@ -183,6 +228,14 @@ class MiniWorldVecEnv(VecEnv):
                        (valid until the next step); infos.truncated / terminated / terminal_row for the whole batch.  With
                        rollout_steps: envs.rollout.bootstrap_truncated(V(envs.terminal.rows), gamma) after the step.  Not with
                        graph=True (that path keeps the non-fused stack)
+    num_levels=L    -> a level set (BatchedMiniWorld.levels_enable; Procgen's num_levels / start_level): every episode is played in one
+                       of L named worlds - level i has the seed level_seeds[i] where given, start_level + i otherwise - chosen on
+                       the device whenever an env is regenerated: level_mode "uniform" (default; level_sampler_seed), "sequential"
+                       (env g's n-th episode plays (g + n * level_stride) mod L; level_stride defaults to num_envs) or "table"
+                       (envs.levels.next_level).  `seed` is then unused.  Every info dict carries info['level_seed'] and, where
+                       done, info['prev_level_seed']; infos.level / prev_level for the whole batch; envs.levels holds the device
+                       views and the per-level tallies.  evaluate() restarts the episode numbering, so every checkpoint plays
+                       the same levels.  Not with graph=True in this version
     feature_info    -> every info dict carries "feature" (length-2 zeros) as the fork's PPO loop
                        requires (pytorch-a2c-ppo-acktr/main.py:614-619)
     graph=True      -> after two eager steps the whole step (mwb_step's kernels on both streams, the frame-stack /
@@ -197,15 +250,23 @@ class MiniWorldVecEnv(VecEnv):
 
     def __init__(self, env_id, num_envs, seed=1, device=0, domain_rand=False, transpose=True, to_float=True,
                  frame_stack=0, torch_api=True, feature_info=False, first_env_index=0, graph=False, greyscale=False, frame_skip=1,
-                 rollout_steps=0, rollout_learner=False, monitor=0, monitor_quota_max=8, terminal_obs=0, **kwargs):
+                 rollout_steps=0, rollout_learner=False, monitor=0, monitor_quota_max=8, terminal_obs=0, num_levels=0, start_level=0,
+                 level_seeds=None, level_mode="uniform", level_sampler_seed=0, level_stride=None, **kwargs):
         import torch
-        from .batch import BatchedMiniWorld, check_terminal_args
+        from .batch import BatchedMiniWorld, check_terminal_args, check_levels_args
         from . import _lib
         self.torch = torch
         self.greyscale = bool(greyscale)
         if terminal_obs and graph:
             raise ValueError("terminal_obs cannot be combined with graph=True: the captured step keeps the non-fused frame stack, "
                              "the terminal rows are built from the fused one")
+        level_args = None
+        if num_levels or level_seeds is not None:   # checked before anything is created
+            if graph:
+                raise ValueError("num_levels cannot be combined with graph=True in this version (level sets under a captured graph "
+                                 "are not built)")
+            level_args = check_levels_args(num_levels if num_levels else len(level_seeds), start_level, level_seeds, level_mode,
+                                           level_sampler_seed, True, level_stride, num_envs)
         if terminal_obs:   # True: a row for every env; checked before anything is created
             terminal_obs = check_terminal_args(None if terminal_obs is True else terminal_obs, num_envs, kwargs.get("auto_reset", True))[0]
         if rollout_steps and graph:
@@ -247,6 +308,11 @@ class MiniWorldVecEnv(VecEnv):
         if self.terminal is not None:
             self._term_by_env = self.greyscale and not self.nstack
             self._term_obs = self.terminal.grey if self._term_by_env else self.terminal.rows
+        # level sets: every regeneration from here on starts from a level seed (the batch's own seed() no longer matters)
+        self.levels = None
+        if level_args is not None:
+            L_, start_, seeds_, mode_, sseed_, tally_, stride_ = level_args
+            self.levels = b.levels_enable(L_, start_, seeds_, mode_, sseed_, tally_, stride_)
         # the trainer's RolloutStorage on the device: pushed by reset() and by the device part of every step
         self.rollout = b.rollout_enable(int(rollout_steps), nstack=self.nstack or 1, grey=self.greyscale,
                                         learner=bool(rollout_learner)) if rollout_steps else None
@@ -281,6 +347,7 @@ class MiniWorldVecEnv(VecEnv):
         self._term_none = (np.zeros(num_envs, bool), np.zeros(num_envs, bool), np.full(num_envs, -1, np.int64))
         for arr in self._term_none:
             arr.setflags(write=False)
+        self._h_levels = pin((2, num_envs), torch.int32) if self.levels is not None else None   # index | prev_index, 8 bytes per env
         self._h_mon = None   # the monitor's host pack: one more copy beside the pack's
         if self.monitor is not None:
             mo = self.monitor.host_pack_offsets
@@ -340,6 +407,8 @@ class MiniWorldVecEnv(VecEnv):
             self._h_taken.copy_(b.taken, non_blocking=True)   # same stream, ahead of step_wait's one wait
         if self._h_cause is not None:
             self._h_cause.copy_(self.terminal.cause, non_blocking=True)
+        if self._h_levels is not None:
+            self._h_levels.copy_(self.levels.index_pair, non_blocking=True)
         return obs
 
     def step_async(self, actions, mask=None):
@@ -410,6 +479,8 @@ class MiniWorldVecEnv(VecEnv):
             ep.update(truncated=trunc, terminated=term, terminal_row=row, terminal_obs=self._term_obs)
             if self._term_by_env:   # (the grey frames are indexed by env, and every env that ended has one)
                 ep.update(terminal_index=np.where(trunc | term, np.arange(self.num_envs), -1))
+        if self._h_levels is not None:   # Procgen's info['level_seed'] / ['prev_level_seed']
+            ep.update(level_infos(self._h_levels.numpy(), dones, self.levels.start_level, self.levels._seeds))
         if b.has_health:   # CollectHealth: info['health'] (delivered in feature[:, 0])
             infos = LazyInfos(self.num_envs, health=self._h_feat[:, 0].astype(np.float64), skipped=sk, default_feature=self.feature_info, taken=tk, **ep)
         elif b.has_goal_pos:   # the T-maze family: info['goal_pos'] (tmaze.py:66,206) and, where produced, info['feature']
@@ -450,7 +521,7 @@ class MiniWorldVecEnv(VecEnv):
         self.batch.close()
 
 
-def evaluate(envs, act, episodes_per_env=1, max_calls=None):
+def evaluate(envs, act, episodes_per_env=1, max_calls=None, restart_levels=True):
     """Evaluate a policy on a vectorised env: every env plays exactly `episodes_per_env` episodes, then retires (it is named in
     the `mask` of every later step and stands still).  act(obs) -> actions for envs.step.  Returns (returns, lengths): float64
     and int32 [episodes_per_env, N] device tensors, env e's j-th episode in [j, e]; lengths in env steps.
@@ -462,7 +533,11 @@ def evaluate(envs, act, episodes_per_env=1, max_calls=None):
 
     Needs MiniWorldVecEnv(monitor=K, monitor_quota_max >= episodes_per_env).  Sets the quota, resets, and steps until the
     monitor's `remaining` - read with every step's one wait, no extra synchronisation - is 0, or after max_calls steps (then
-    the unfinished cells hold NaN / -1).  The quota stays set; envs.monitor.set_quota(0) before training goes on."""
+    the unfinished cells hold NaN / -1).  The quota stays set; envs.monitor.set_quota(0) before training goes on.
+
+    Where the view has level sets (num_levels=L) and restart_levels is true, the episode numbering is restarted before the reset
+    (envs.levels.restart(clear_tally=False)): the levels an env plays depend only on its index and the episode number, so the same
+    call visits the same levels for every checkpoint."""
     mon = envs.monitor
     if mon is None:
         raise ValueError("evaluate needs a monitor: MiniWorldVecEnv(..., monitor=K)")
@@ -470,6 +545,8 @@ def evaluate(envs, act, episodes_per_env=1, max_calls=None):
     if not 1 <= q <= mon.quota_max:
         raise ValueError("evaluate: episodes_per_env %d outside 1 .. monitor_quota_max = %d" % (q, mon.quota_max))
     mon.set_quota(q)
+    if restart_levels and getattr(envs, "levels", None) is not None:
+        envs.levels.restart(clear_tally=False)
     obs = envs.reset()
     mask, calls = None, 0
     while max_calls is None or calls < max_calls:

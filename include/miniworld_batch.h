@@ -630,6 +630,67 @@ int mwb_terminal_dropped(mwb_handle *h, unsigned long long *envs);     /* synchr
  * cursor is at least 1. */
 int mwb_rollout_bootstrap(mwb_handle *h, const float *value_rows_dev, double gamma, void *stream);
 
+/* ---- level sets: every episode's world from a level seed chosen on the device -------------------------- */
+/* replaces: Procgen's `num_levels` / `start_level` (a finite, named set of worlds to train on, unseen ones to test on), and in
+ * the reference `env.seed(s); env.reset()` per episode (miniworld.py seed(): `self.rand = RandGen(seed)`), which for a batch is
+ * mwb_seed on the host: one SHA-512 and one init_by_array per env, 2500 bytes copied per env, and a full reset.
+ *
+ * Opt-in: a handle that never calls mwb_levels_enable launches exactly what it launched before.  On an enabled handle EVERY
+ * regeneration of an env - the auto-reset inside mwb_step / mwb_step_i64 / mwb_step_repeat, mwb_reset(mask), mwb_reset(NULL) -
+ * first overwrites the env's generator row rng[e][0..624] with exactly what mwb_seed writes for the seed of a chosen level
+ * (SHA-512 of the decimal string, first 8 bytes, high limb dropped when zero; init_by_array; position 624).  The episode that
+ * follows therefore equals the first episode of a reference env on which `env.seed(level_seed); env.reset()` ran, its
+ * domain-randomisation draws at every step included.  The T-maze family's episode_count / task_step_count / goal_idx carry on
+ * across it, as they do across env.seed() in the reference.
+ *
+ * A set has L = num_levels levels, 1 <= L <= 2^31 - 1.  Level i has the seed level_seeds_host[i] where a table was given
+ * (L <= 2^24; copied to the device), start_level + i in uint64 arithmetic otherwise.  Per env the device keeps index (i32, the
+ * level it is in, -1 before its first assignment), prev_index (i32, the level of its previous episode or -1), episode_no (i64,
+ * assignments since enable or restart) and next_level (i32, a request, -1 = none).  The level of an assignment depends only on
+ * (g, n, request), g = env_offset + e, n = episode_no[e], never on the order of the regenerated envs:
+ *   MWB_LEVELS_SEQUENTIAL  i = (g + n * env_stride) mod L; with L = q * env_stride, q episodes per env visit every level once
+ *   MWB_LEVELS_UNIFORM     a = mix(sampler_seed + GOLD * (g + 1)), h = mix(a + GOLD * (n + 1)), i = (h * L) >> 64, with
+ *                          GOLD = 0x9E3779B97F4A7C15 and mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *                          z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   MWB_LEVELS_TABLE       next_level[e] where 0 <= next_level[e] < L, the UNIFORM level otherwise; a value other than -1 that is
+ *                          out of range is counted (mwb_levels_rejected) and no address is formed from it; the entry is consumed
+ *                          either way (set to -1).  The caller refills next_level whenever it likes.
+ * mode and sampler_seed live in device memory: mwb_levels_restart sets them, zeroes episode_no and (clear_tally) the tallies in
+ * a small kernel on `stream`; index and prev_index stay.
+ *
+ * MWB_LEVELS_TALLY (L <= 2^22): u64 tallies[3][L] - episodes, env steps and successes (float64 reward > 0 on the ending
+ * transition: the sparse-reward tasks' success; it means little for PickupObjs and CollectHealth) of the level an env LEAVES,
+ * added with integer atomics in step passes only and only where index[e] >= 0.  mwb_reset abandons episodes and tallies nothing.
+ *
+ * mwb_copy_envs gives a destination its source's index where both handles have level sets (episode_no, prev_index and
+ * next_level stay the destination's own: twins agree until the episode ends, then follow their own (g, n)); a destination
+ * filled from a handle without level sets gets index -1, unknown, and is not tallied when it ends.
+ *
+ * mwb_levels_enable: once per handle; MWB_EINVAL for num_levels outside 1 .. 2^31 - 1, a table with more than 2^24 levels,
+ * env_stride < 1, env_offset < 0, an unknown mode or flag, MWB_LEVELS_TALLY beyond 2^22 levels.  It marks the handle seeded:
+ * mwb_seed is no longer required. */
+#define MWB_LEVELS_SEQUENTIAL 0
+#define MWB_LEVELS_UNIFORM    1
+#define MWB_LEVELS_TABLE      2
+#define MWB_LEVELS_TALLY      1u
+int mwb_levels_enable(mwb_handle *h, int64_t num_levels, uint64_t start_level, const uint64_t *level_seeds_host /* or NULL */,
+                      int mode, uint64_t sampler_seed, int64_t env_offset, int64_t env_stride, unsigned flags);
+int mwb_levels_restart(mwb_handle *h, int mode, uint64_t sampler_seed, int clear_tally, void *stream);
+/* the device arrays (fixed for the handle's lifetime) and the parameters.  Tag only, as struct mwb_rollout_info */
+struct mwb_levels_info {
+    int32_t *index, *prev_index, *next_level;   /* i32 [N] each; prev_index == index + N (one copy mirrors both) */
+    int64_t *episode_no;                        /* i64 [N] */
+    unsigned long long *tallies;                /* u64 [3][L]: episodes, env steps, successes; NULL without MWB_LEVELS_TALLY */
+    const uint64_t *level_seeds;                /* u64 [L] on the device, NULL without a table */
+    int64_t num_levels;
+    uint64_t start_level, sampler_seed;         /* sampler_seed and mode: as enable / restart set them last */
+    int64_t env_offset, env_stride;
+    int32_t mode;
+    uint32_t flags;
+};
+int mwb_levels_info(mwb_handle *h, struct mwb_levels_info *out);      /* MWB_ESTATE before mwb_levels_enable */
+int mwb_levels_rejected(mwb_handle *h, unsigned long long *entries);   /* synchronous; reads and clears */
+
 /* World generation cannot fail for the four tasks with sane arguments; if it ever does (a portal outside
  * its wall, more than one portal on an edge, a placement that finds no free spot in 100000 draws - the
  * reference would assert or spin) the kernel flags it. Synchronous: returns MWB_ESTATE if any env of the
