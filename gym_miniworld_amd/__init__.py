@@ -7,11 +7,11 @@ family (TMaze, TMazeLeft / Right, TMazeDynamic, the two-box variants).  See DESI
 from .params import DEFAULT_PARAMS, DomainParams  # noqa: F401
 
 __all__ = ["BatchedMiniWorld", "MiniWorldVecEnv", "MiniWorldEnv", "make", "make_vec_envs", "DEFAULT_PARAMS",
-           "DomainParams", "ENV_SPECS", "Monitor", "evaluate", "Levels", "level_of"]
+           "DomainParams", "ENV_SPECS", "Monitor", "evaluate", "Levels", "level_of", "Augment"]
 
 
 def __getattr__(name):   # lazy: importing the package must not need torch / the GPU
-    if name in ("BatchedMiniWorld", "ENV_SPECS", "Monitor", "Levels", "level_of"):
+    if name in ("BatchedMiniWorld", "ENV_SPECS", "Monitor", "Levels", "level_of", "Augment"):
         from . import batch
         return getattr(batch, name)
     if name in ("MiniWorldVecEnv", "make_vec_envs", "VecEnv", "evaluate"):

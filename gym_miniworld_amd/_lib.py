@@ -38,6 +38,8 @@ TERMINAL_FLOAT = 1           # MWB_TERMINAL_FLOAT
 LEVELS_SEQUENTIAL, LEVELS_UNIFORM, LEVELS_TABLE = 0, 1, 2   # MWB_LEVELS_*: how a level set hands out levels
 LEVELS_TALLY = 1             # MWB_LEVELS_TALLY
 LEVELS_MAX, LEVELS_MAX_TABLE, LEVELS_MAX_TALLY = 2 ** 31 - 1, 2 ** 24, 2 ** 22   # csrc/mwb_levels_map.h
+WINDOW_MAX_OUT, WINDOW_MAX_OFFSET = 1024, 32767   # csrc/mwb_rollout_window_map.h
+WINDOW_BORDER_EDGE, WINDOW_BORDER_ZERO = 0, 1
 
 
 class MwbConfig(ctypes.Structure):
@@ -79,6 +81,10 @@ class MwbRolloutInfo(ctypes.Structure):   # struct mwb_rollout_info
         ("num_steps", ctypes.c_int32), ("nstack", ctypes.c_int32), ("grey", ctypes.c_int32), ("cursor", ctypes.c_int32),
         ("base", ctypes.c_int32), ("pad", ctypes.c_int32),
     ]
+
+
+class MwbRolloutWindow(ctypes.Structure):   # struct mwb_rollout_window
+    _fields_ = [(n, ctypes.c_int32) for n in ("out_w", "out_h", "border", "dx_lo", "dx_hi", "dy_lo", "dy_hi", "pad")]
 
 
 class MwbRolloutLearnerInfo(ctypes.Structure):   # struct mwb_rollout_learner_info
@@ -125,6 +131,7 @@ EXPORTS = [
     "mwb_monitor_enable", "mwb_monitor_update", "mwb_monitor_clear", "mwb_monitor_quota", "mwb_monitor_info", "mwb_monitor_read",
     "mwb_terminal_enable", "mwb_terminal_info", "mwb_terminal_dropped", "mwb_rollout_bootstrap",
     "mwb_levels_enable", "mwb_levels_restart", "mwb_levels_info", "mwb_levels_rejected",
+    "mwb_rollout_window_offsets", "mwb_rollout_gather_window",
 ]
 
 _lib = None
@@ -217,6 +224,9 @@ def load():
         L.mwb_levels_restart.argtypes = [vp, i32, ctypes.c_uint64, i32, vp]
         L.mwb_levels_info.argtypes = [vp, ctypes.POINTER(MwbLevelsInfo)]
         L.mwb_levels_rejected.argtypes = [vp, ctypes.POINTER(ctypes.c_ulonglong)]
+    if hasattr(L, "mwb_rollout_gather_window"):   # (an older library through MWB_LIB)
+        L.mwb_rollout_window_offsets.argtypes = [vp, ctypes.POINTER(MwbRolloutWindow), ctypes.c_uint64, ctypes.c_uint64, vp, i32, vp, vp]
+        L.mwb_rollout_gather_window.argtypes = [vp, vp, i32, ctypes.POINTER(MwbRolloutWindow), vp, vp, i32, vp]
     if hasattr(L, "mwb_bulk_variant"):   # (an older library loaded through MWB_LIB for a kernel A/B has none; build() checks EXPORTS)
         L.mwb_bulk_variant.argtypes = [vp]
     L.mwb_timing_read.argtypes = [vp] +[ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(i32)]

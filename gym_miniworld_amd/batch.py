@@ -158,11 +158,117 @@ def check_rollout_column_indices(index, num_steps, num_envs):
     return _check_index_list(index, int(num_steps) * int(num_envs), "minibatch", "num_steps * num_envs")
 
 
+class Augment:
+    """A per-row random window for Rollout.gather / obs / minibatch / feed_forward_generator (mwb_rollout_gather_window): the image
+    augmentation of a minibatch applied while the rows are rebuilt from their single frames.  One draw per stacked observation,
+    shared by all of its frames:
+        Augment.shift(pad, seed=0)        DrQ / RAD random shift: replicate-pad by pad, crop back to W x H
+        Augment.crop(w, h, seed=0)        random crop to w x h <= W x H
+        Augment.center_crop(w, h)         the evaluation counterpart of crop
+        Augment.translate(w, h, seed=0)   the frame at a random place of a black w x h >= W x H canvas
+    `seed` and the counter `calls` key the draw (csrc/mwb_rollout_window_map.h): the offsets of gather index i in call c are
+    offsets_of([i], c) wherever a permutation puts the row.  An Augment is bound to a frame size at first use (bind)."""
+
+    def __init__(self, kind, a, b=None, seed=0):
+        if kind not in ("shift", "crop", "center_crop", "translate"):
+            raise ValueError("Augment: unknown kind %r" % (kind,))
+        for v in (a,) if kind == "shift" else (a, b):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("Augment.%s: integer parameters required, not %r" % (kind, v))
+        if kind == "shift" and not 0 <= a <= _lib.WINDOW_MAX_OFFSET:
+            raise ValueError("Augment.shift: pad %d outside 0 .. %d" % (a, _lib.WINDOW_MAX_OFFSET))
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+            raise ValueError("Augment: seed must be an integer, not %r" % (seed,))
+        self.kind, self.params, self.seed, self.calls = kind, (int(a),) if kind == "shift" else (int(a), int(b)), int(seed) & _M64, 0
+        self.frame = None    # (W, H) once bound
+        self.window = None   # (out_w, out_h, border, dx_lo, dx_hi, dy_lo, dy_hi) once bound
+
+    @classmethod
+    def shift(cls, pad, seed=0):
+        return cls("shift", pad, seed=seed)
+
+    @classmethod
+    def crop(cls, w, h, seed=0):
+        return cls("crop", w, h, seed=seed)
+
+    @classmethod
+    def center_crop(cls, w, h):
+        return cls("center_crop", w, h)
+
+    @classmethod
+    def translate(cls, w, h, seed=0):
+        return cls("translate", w, h, seed=seed)
+
+    def bind(self, W, H):
+        """Fix the frame size the window is cut from -> the window (out_w, out_h, border, dx_lo, dx_hi, dy_lo, dy_hi).  ValueError
+        for a second, different size, for a crop larger or a translate smaller than the frame and for a window outside the
+        library's limits (out sizes 1 .. 1024, out_w * out_h a multiple of 4, bounds within -32767 .. 32767)."""
+        W, H = int(W), int(H)
+        if self.frame is not None:
+            if self.frame != (W, H):
+                raise ValueError("Augment.%s: bound to %d x %d frames, not %d x %d" % ((self.kind,) + self.frame + (W, H)))
+            return self.window
+        kind, p = self.kind, self.params
+        if kind == "shift":
+            win = (W, H, _lib.WINDOW_BORDER_EDGE, -p[0], p[0], -p[0], p[0])
+        elif kind in ("crop", "center_crop"):
+            w, h = p
+            if not (1 <= w <= W and 1 <= h <= H):
+                raise ValueError("Augment.%s: %d x %d does not fit the %d x %d frame" % (kind, w, h, W, H))
+            mid = ((W - w) // 2, (H - h) // 2)
+            win = (w, h, _lib.WINDOW_BORDER_EDGE) + ((0, W - w, 0, H - h) if kind == "crop" else (mid[0], mid[0], mid[1], mid[1]))
+        else:
+            w, h = p
+            if w < W or h < H:
+                raise ValueError("Augment.translate: the %d x %d canvas is smaller than the %d x %d frame" % (w, h, W, H))
+            win = (w, h, _lib.WINDOW_BORDER_ZERO, -(w - W), 0, -(h - H), 0)
+        if not (1 <= win[0] <= _lib.WINDOW_MAX_OUT and 1 <= win[1] <= _lib.WINDOW_MAX_OUT):
+            raise ValueError("Augment.%s: output %d x %d outside 1 .. %d" % (kind, win[0], win[1], _lib.WINDOW_MAX_OUT))
+        if (win[0] * win[1]) % 4:
+            raise ValueError("Augment.%s: out_w * out_h = %d x %d must be a multiple of 4" % (kind, win[0], win[1]))
+        if max(abs(v) for v in win[3:]) > _lib.WINDOW_MAX_OFFSET:
+            raise ValueError("Augment.%s: offset bounds outside -%d .. %d" % (kind, _lib.WINDOW_MAX_OFFSET, _lib.WINDOW_MAX_OFFSET))
+        self.frame, self.window = (W, H), win
+        return win
+
+    def offsets_of(self, index, call=None):
+        """The draws of the gather indices `index` in call `call` (None: the next one, self.calls) -> int32 [B, 2] = (dx, dy):
+        csrc/mwb_rollout_window_map.h restated with Python integers.  The Augment must be bound (bind, or a first gather)."""
+        if self.window is None:
+            raise ValueError("Augment.%s: not bound to a frame size yet (bind(W, H))" % self.kind)
+        _, _, _, dx_lo, dx_hi, dy_lo, dy_hi = self.window
+        call = self.calls if call is None else int(call)
+        key = _mix64((self.seed + _GOLD * (call + 1)) & _M64)
+        out = np.empty((np.size(index), 2), np.int32)
+        for i, ix in enumerate(np.asarray(index, dtype=object).reshape(-1)):
+            h = _mix64((key + _GOLD * ((int(ix) & _M64) + 1)) & _M64)
+            out[i, 0] = dx_lo + (((h >> 32) * (dx_hi - dx_lo + 1)) >> 32)
+            out[i, 1] = dy_lo + (((h & 0xffffffff) * (dy_hi - dy_lo + 1)) >> 32)
+        return out
+
+    def _struct(self, W, H):
+        return _lib.MwbRolloutWindow(*self.bind(W, H), 0)
+
+
+def check_window_offsets(offsets, count):
+    """What Rollout.gather refuses before anything is launched, for offsets that live on the host: ValueError unless they are
+    integers of shape [count, 2] that fit int32.  Returns them as an int32 array."""
+    a = np.asarray(offsets)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("rollout gather: offsets must be integers, not %s" % a.dtype)
+    if a.shape != (int(count), 2):
+        raise ValueError("rollout gather: offsets of shape %s for %d rows ([B, 2] = (dx, dy) required)" % (a.shape, count))
+    if a.size and (a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1):
+        raise ValueError("rollout gather: offsets must fit int32")
+    return a.astype(np.int32)
+
+
 class Rollout:
     """The observation half of RolloutStorage (pytorch-a2c-ppo-acktr/storage.py) on the device, every frame stored once
     (BatchedMiniWorld.rollout_enable; include/miniworld_batch.h at mwb_rollout_enable):
         ro.push(after_reset=True) after reset(), ro.push() after every step()     rollouts.obs[step + 1].copy_(obs) + insert()
         ro.gather(idx)                                                            obs[:-1].view(-1, ...)[idx]
+        ro.gather(idx, augment=Augment.shift(4))                                  ... followed by the trainer's random shift / crop
         ro.after_update()                                                         rollouts.after_update()
     rewards [T, N], masks [T+1, N], features [T+1, N, 2] and ages [T+1, N] are zero-copy views of the library's arrays.
 
@@ -242,32 +348,74 @@ class Rollout:
         _lib.check(self.L.mwb_rollout_push(b.h, int(bool(after_reset)), f, b._stream()))
         self._keep = fresh   # alive until the asynchronous kernel has consumed it
 
-    def gather(self, index, dtype=None):
+    def gather(self, index, dtype=None, augment=None, offsets=None, return_offsets=False):
         """index[i] = t * N + e, t in 0 .. step -> [B, nstack * C, W, H]: the stacked observations VecPyTorchFrameStack held at
         those steps, bit for bit; float32, or dtype=torch.uint8 (RGB only).  A LongTensor on the batch's device is read in
         place, without synchronisation: a row whose index is out of range comes back as zeros and is counted (rejected()).
-        Anything that lives on the host is checked first by check_rollout_indices: ValueError, nothing is launched."""
+        Anything that lives on the host is checked first by check_rollout_indices: ValueError, nothing is launched.
+
+        augment (an Augment): the rows come back through its window, [B, nstack * C, out_w, out_h], in the same single pass
+        (mwb_rollout_gather_window).  offsets=None draws every row's (dx, dy) on the device with (augment.seed, augment.calls) and
+        then increments augment.calls; an int32 [B, 2] tensor on the batch's device is read in place and clamped to the window's
+        ranges on the device; host data is checked first (check_window_offsets).  return_offsets=True: (rows, the clamped int32
+        [B, 2] device tensor that was used)."""
         torch, b = self.torch, self.batch
         dtype = torch.float32 if dtype is None else dtype
         if dtype not in (torch.float32, torch.uint8):
             raise ValueError("rollout gather: dtype must be torch.float32 or torch.uint8")
+        if augment is None and (offsets is not None or return_offsets):
+            raise ValueError("rollout gather: offsets / return_offsets need an augment")
+        win = None if augment is None else augment._struct(b.W, b.H)   # ValueError before anything is launched
         if torch.is_tensor(index) and index.device == b.device:
             idx = index.reshape(-1).to(torch.int64).contiguous()
         else:
             host = index.cpu().numpy() if torch.is_tensor(index) else index
             idx = torch.from_numpy(check_rollout_indices(host, self.step, self.num_envs)).to(b.device)
+        if augment is not None:
+            out, used = self._gather_window(idx, dtype, augment, win, offsets, None)
+            return (out, used) if return_offsets else out
         out = torch.empty((idx.numel(), self.channels, b.W, b.H), dtype=dtype, device=b.device)
         _lib.check(self.L.mwb_rollout_gather(b.h, ctypes.c_void_p(idx.data_ptr()), int(idx.numel()), ctypes.c_void_p(out.data_ptr()),
                                              1 if dtype == torch.float32 else 0, b._stream()))
         self._keep_idx = idx
         return out
 
-    def obs(self, t, dtype=None):
-        """rollouts.obs[t]: the stacked observations of every env at logical time t (0 .. step)"""
+    def _gather_window(self, idx, dtype, augment, win, offsets, call):
+        """the windowed gather of the device index list idx -> (rows, clamped offsets).  offsets None: drawn with call number
+        `call`; call None: augment.calls, which then advances"""
+        torch, b = self.torch, self.batch
+        B = int(idx.numel())
+        if offsets is None:
+            offs = torch.empty((B, 2), dtype=torch.int32, device=b.device)
+            number = augment.calls if call is None else call
+            _lib.check(self.L.mwb_rollout_window_offsets(b.h, ctypes.byref(win), augment.seed, number, ctypes.c_void_p(idx.data_ptr()), B,
+                                                         ctypes.c_void_p(offs.data_ptr()), b._stream()))
+            if call is None:
+                augment.calls += 1
+            used = offs   # drawn inside the ranges
+        else:
+            if torch.is_tensor(offsets) and offsets.device == b.device:
+                if offsets.dtype != torch.int32 or tuple(offsets.shape) != (B, 2):
+                    raise ValueError("rollout gather: offsets on the device must be int32 [%d, 2], not %s %s" % (B, offsets.dtype, tuple(offsets.shape)))
+                offs = offsets.contiguous()
+            else:
+                host = offsets.cpu().numpy() if torch.is_tensor(offsets) else offsets
+                offs = torch.from_numpy(check_window_offsets(host, B)).to(b.device)
+            lo = torch.tensor([win.dx_lo, win.dy_lo], dtype=torch.int32, device=b.device)
+            hi = torch.tensor([win.dx_hi, win.dy_hi], dtype=torch.int32, device=b.device)
+            used = torch.minimum(torch.maximum(offs, lo), hi)   # what the kernel computes from (it reads offs itself)
+        out = torch.empty((B, self.channels, win.out_w, win.out_h), dtype=dtype, device=b.device)
+        _lib.check(self.L.mwb_rollout_gather_window(b.h, ctypes.c_void_p(idx.data_ptr()), B, ctypes.byref(win), ctypes.c_void_p(offs.data_ptr()),
+                                                    ctypes.c_void_p(out.data_ptr()), 1 if dtype == torch.float32 else 0, b._stream()))
+        self._keep_idx, self._keep_offs = idx, offs
+        return out, used
+
+    def obs(self, t, dtype=None, augment=None):
+        """rollouts.obs[t]: the stacked observations of every env at logical time t (0 .. step); augment: as gather()"""
         t = int(t)
         if not 0 <= t <= self.step:
             raise ValueError("rollout obs: t = %d outside 0 .. %d" % (t, self.step))
-        return self.gather(self._arange + t * self.num_envs, dtype=dtype)
+        return self.gather(self._arange + t * self.num_envs, dtype=dtype, augment=augment)
 
     def after_update(self):
         _lib.check(self.L.mwb_rollout_after_update(self.batch.h, self.batch._stream()))
@@ -331,20 +479,25 @@ class Rollout:
         _lib.check(self.L.mwb_rollout_bootstrap(b.h, ctypes.c_void_p(v.data_ptr()), float(gamma), b._stream()))
         self._keep_boot = v   # alive until the asynchronous kernel has consumed it
 
-    def minibatch(self, index, advantages=None):
+    def minibatch(self, index, advantages=None, augment=None):
         """index[i] = t * N + e with t in 0 .. T - 1 (the flat indices of the reference's [:-1] views) ->
         (obs, actions, returns, masks, old_log_probs, adv, values): obs as gather() returns it, the others [B, 1].  One gather and
         one kernel for the six small columns.  advantages [T, N]: the caller's (normalised) ones; None: the stored advantages.
         An index list on the host is checked first (check_rollout_column_indices: ValueError, nothing launched); a LongTensor on
-        the device is read in place, a row out of range comes back as zeros and is counted (rejected())."""
+        the device is read in place, a row out of range comes back as zeros and is counted (rejected()).
+        augment (an Augment): obs is gather(index, augment=augment) - one draw, augment.calls advances; the columns are unchanged."""
+        return self._minibatch(index, advantages, augment, None)
+
+    def _minibatch(self, index, advantages, augment, call):
         torch, b = self.torch, self.batch
+        win = None if augment is None else augment._struct(b.W, b.H)
         if torch.is_tensor(index) and index.device == b.device:
             idx = index.reshape(-1).to(torch.int64).contiguous()
         else:
             host = index.cpu().numpy() if torch.is_tensor(index) else index
             idx = torch.from_numpy(check_rollout_column_indices(host, self.num_steps, self.num_envs)).to(b.device)
         adv = None if advantages is None else self._column("minibatch: advantages", advantages, self.num_steps * self.num_envs, (torch.float32,))
-        obs = self.gather(idx)
+        obs = self.gather(idx) if augment is None else self._gather_window(idx, torch.float32, augment, win, None, call)[0]
         B = idx.numel()
         cols = torch.empty((5, B, 1), dtype=torch.float32, device=b.device)
         act = torch.empty((B, 1), dtype=torch.int64, device=b.device)
@@ -353,12 +506,15 @@ class Rollout:
         self._keep_adv = adv
         return obs, act, cols[0], cols[4], cols[2], cols[3], cols[1]
 
-    def feed_forward_generator(self, advantages, num_mini_batch, generator=None):
+    def feed_forward_generator(self, advantages, num_mini_batch, generator=None, augment=None):
         """RolloutStorage.feed_forward_generator (storage.py:110-131): yields (obs, None, actions, returns, masks, old_log_probs,
         adv_targ) - None where the reference has the recurrent hidden states - over a random permutation of the T * N transitions
         drawn on the device (generator: a torch.Generator of the batch's device), cut into batches of T * N // num_mini_batch as
-        BatchSampler(drop_last=False) cuts them: the last one may be shorter."""
+        BatchSampler(drop_last=False) cuts them: the last one may be shorter.
+        augment (an Augment): every obs comes through its window with ONE call number for the whole pass - augment.calls advances
+        once, when the pass is exhausted - so every transition gets exactly one draw per epoch and a new one the next epoch."""
         torch = self.torch
+        call = None if augment is None else augment.calls
         batch_size = self.num_steps * self.num_envs
         assert batch_size >= num_mini_batch, (
             "PPO requires the number of processes ({}) * number of steps ({}) = {} to be greater than or equal to the number of "
@@ -366,8 +522,10 @@ class Rollout:
         mini_batch_size = batch_size // num_mini_batch
         perm = torch.randperm(batch_size, device=self.batch.device, generator=generator)
         for first in range(0, batch_size, mini_batch_size):
-            obs, act, ret, mask, logp, adv, _ = self.minibatch(perm[first:first + mini_batch_size], advantages)
+            obs, act, ret, mask, logp, adv, _ = self._minibatch(perm[first:first + mini_batch_size], advantages, augment, call)
             yield obs, None, act, ret, mask, logp, adv
+        if augment is not None:
+            augment.calls += 1
 
     def rejected(self):
         """rows of gathers whose index was out of range since the last call (synchronous)"""

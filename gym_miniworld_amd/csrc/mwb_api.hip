@@ -17,6 +17,7 @@
 #include "mwb_internal.h"
 #include "mwb_lds_layout.h"
 #include "mwb_rollout_map.h"
+#include "mwb_rollout_window_map.h"
 #include "mwb_monitor_map.h"
 #include "mwb_levels_map.h"
 #include "mwb_returns_scan.h"
@@ -968,6 +969,50 @@ extern "C" int mwb_rollout_gather(mwb_handle *h, const int64_t *index_dev, int c
     USE_DEVICE(h->cfg.device);
     mwb_launch_rollout_gather(r, index_dev, count, out_dev, dtype, (hipStream_t)stream);
     return check_launch("rollout_gather_kernel");
+}
+
+// the windowed gather: the rule is mwb_rollout_window_map.h, the kernels mwb_rollout_window.hip
+static int window_of(const mwb_handle *h, const struct mwb_rollout_window *w, const char *who, MwbWindow &out) {
+    if (int limit = mwb_window_check(w->out_w, w->out_h, w->border, w->dx_lo, w->dx_hi, w->dy_lo, w->dy_hi))
+        return set_err(MWB_EINVAL, std::string(who) + ": " + mwb_window_limit_text(limit));
+    out = MwbWindow{h->dev.W, h->dev.H, w->out_w, w->out_h, w->border, w->dx_lo, w->dx_hi, w->dy_lo, w->dy_hi};
+    return MWB_OK;
+}
+
+extern "C" int mwb_rollout_window_offsets(mwb_handle *h, const struct mwb_rollout_window *w, uint64_t seed, uint64_t call,
+                                          const int64_t *index_dev, int count, int32_t *offsets_dev, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_window_offsets: null handle");
+    if (!w) return set_err(MWB_EINVAL, "mwb_rollout_window_offsets: null argument");
+    MwbWindow win;
+    if (int rc = window_of(h, w, "mwb_rollout_window_offsets", win)) return rc;
+    if (count < 0) return set_err(MWB_EINVAL, "mwb_rollout_window_offsets: count < 0");
+    if (count == 0) return MWB_OK;
+    if (!index_dev || !offsets_dev) return set_err(MWB_EINVAL, "mwb_rollout_window_offsets: null argument");
+    if ((uintptr_t)offsets_dev & 7) return set_err(MWB_EINVAL, "mwb_rollout_window_offsets: offsets_dev must be 8-byte aligned");
+    USE_DEVICE(h->cfg.device);
+    mwb_launch_rollout_window_offsets(win, mwb_window_key(seed, call), index_dev, count, offsets_dev, (hipStream_t)stream);
+    return check_launch("rollout_window_offsets_kernel");
+}
+
+extern "C" int mwb_rollout_gather_window(mwb_handle *h, const int64_t *index_dev, int count, const struct mwb_rollout_window *w,
+                                         const int32_t *offsets_dev, void *out_dev, int dtype, void *stream) {
+    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_gather_window: null handle");
+    if (!w) return set_err(MWB_EINVAL, "mwb_rollout_gather_window: null argument");
+    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_gather_window: call mwb_rollout_enable first");
+    const MwbRollout &r = h->rollout;
+    MwbWindow win;
+    if (int rc = window_of(h, w, "mwb_rollout_gather_window", win)) return rc;
+    if (dtype != 0 && dtype != 1) return set_err(MWB_EINVAL, "mwb_rollout_gather_window: dtype must be 0 (uint8) or 1 (float32)");
+    if (r.grey && dtype == 0) return set_err(MWB_EINVAL, "mwb_rollout_gather_window: a grey rollout is gathered as float32 (the reference defines no uint8 grey)");
+    if (count < 0) return set_err(MWB_EINVAL, "mwb_rollout_gather_window: count < 0");
+    if (r.cursor < 0) return set_err(MWB_ESTATE, "mwb_rollout_gather_window: nothing has been pushed yet");
+    if (count == 0) return MWB_OK;
+    if (!index_dev || !offsets_dev || !out_dev) return set_err(MWB_EINVAL, "mwb_rollout_gather_window: null argument");
+    if ((uintptr_t)out_dev & 15) return set_err(MWB_EINVAL, "mwb_rollout_gather_window: out_dev must be 16-byte aligned");
+    if ((uintptr_t)offsets_dev & 7) return set_err(MWB_EINVAL, "mwb_rollout_gather_window: offsets_dev must be 8-byte aligned");
+    USE_DEVICE(h->cfg.device);
+    mwb_launch_rollout_window(r, win, index_dev, count, offsets_dev, out_dev, dtype, (hipStream_t)stream);
+    return check_launch("rollout_window_kernel");
 }
 
 extern "C" int mwb_rollout_after_update(mwb_handle *h, void *stream) {

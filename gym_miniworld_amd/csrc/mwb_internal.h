@@ -374,6 +374,19 @@ void mwb_launch_rollout_push(const MwbRollout &r, int t, int after_reset, const 
 void mwb_launch_rollout_after_update(const MwbRollout &r, hipStream_t s);
 void mwb_launch_rollout_gather(const MwbRollout &r, const int64_t *index, int count, void *out, int out_float, hipStream_t s);
 
+// ---- the windowed gather (mwb_rollout_gather_window; mwb_rollout_window_map.h has the rule): a checked window over W x H frames,
+// passed by value to the kernels of mwb_rollout_window.hip
+struct MwbWindow {
+    int W, H;                             // the stored frame
+    int out_w, out_h, border;             // the output plane; 0 = edge replication, 1 = zeros
+    int dx_lo, dx_hi, dy_lo, dy_hi;       // the ranges a row's offsets are clamped to
+};
+// launch wrappers implemented in mwb_rollout_window.hip.  offsets: int32 [count][2], 8-byte aligned; key = mwb_window_key(seed,
+// call); gather: count > 0 rows, out 16-byte aligned, out_float = 1 for a grey ring
+void mwb_launch_rollout_window_offsets(const MwbWindow &w, uint64_t key, const int64_t *index, int count, int32_t *offsets, hipStream_t s);
+void mwb_launch_rollout_window(const MwbRollout &r, const MwbWindow &w, const int64_t *index, int count, const int32_t *offsets, void *out,
+                               int out_float, hipStream_t s);
+
 // ---- the rollout's learner half (mwb_rollout_learner_enable): the small columns of RolloutStorage and what is computed from them
 struct MwbLearner {
     int64_t *action;                 // [T][N]

@@ -455,6 +455,42 @@ struct mwb_rollout_info {
 int mwb_rollout_info(mwb_handle *h, struct mwb_rollout_info *out);   /* MWB_ESTATE before mwb_rollout_enable */
 int mwb_rollout_rejected(mwb_handle *h, unsigned long long *rows);   /* synchronous; reads and clears */
 
+/* ---- rollout storage: the windowed gather - per-row random shift, crop and translate ---------------- */
+/* replaces: obs_batch = obs[:-1].view(-1, ...)[indices] (storage.py:121) FOLLOWED BY the trainer's image augmentation of that
+ * minibatch (RAD / DrQ random shift with edge replication, random crop, random translate; DrAC / UCB-DrAC), which today costs a
+ * second pass over the float32 tensor.  A window is applied while the row is rebuilt from its single uint8 frames: one pass, no
+ * temporary.  Each row has one offset pair (dx, dy), shared by all of its planes (every frame group, every channel) and clamped
+ * on the device to [dx_lo, dx_hi] x [dy_lo, dy_hi] before anything is computed from it.  With F the row mwb_rollout_gather would
+ * write, [nstack * C][W][H], the windowed row is [nstack * C][out_w][out_h] (csrc/mwb_rollout_window_map.h has the rule as code):
+ *   out[p][x][y] = F[p][sx][sy] with sx = x + dx, sy = y + dy where 0 <= sx < W and 0 <= sy < H; elsewhere
+ *                  F[p][clamp(sx, 0, W-1)][clamp(sy, 0, H-1)] for border 0 (edge replication), 0 for border 1 (zeros).
+ * A zero frame group stays zero under either border.  The named augmentations are settings of this rule:
+ *   random shift by pad    out W x H, border 0, dx and dy in -pad .. pad
+ *   random crop w x h      out w x h <= W x H, dx in 0 .. W - w, dy in 0 .. H - h   (centre crop: both ranges one value)
+ *   random translate       out w x h >= W x H, border 1, dx in -(w - W) .. 0, dy in -(h - H) .. 0
+ * MWB_EINVAL for a window outside the limits: 1 <= out_w, out_h <= 1024; out_w * out_h a multiple of 4 (the frame stack's own
+ * rule); lo <= hi; every bound in -32767 .. 32767; border 0 or 1.  The struct has a tag only, as mwb_rollout_info. */
+struct mwb_rollout_window { int32_t out_w, out_h, border, dx_lo, dx_hi, dy_lo, dy_hi, pad; };
+/* replaces: the augmentation's own random draw (torch.randint of the pad / crop positions).  offsets_dev[i] = the draw of
+ * index_dev[i] under (seed, call): device int32 [count][2] = (dx, dy), 8-byte aligned.  With mix = splitmix64's finaliser and
+ * G = 0x9E3779B97F4A7C15 (the level sampler's recipe, uint64 arithmetic):
+ *   key = mix(seed + G * (call + 1)), h = mix(key + G * ((uint64)index + 1)),
+ *   dx = dx_lo + (((h >> 32) * (dx_hi - dx_lo + 1)) >> 32), dy = dy_lo + (((h & 0xffffffff) * (dy_hi - dy_lo + 1)) >> 32).
+ * The draw is keyed by the index, not by the row's place in the minibatch: a transition gets the same draw wherever a permutation
+ * puts it, and a new one when `call` changes.  Any int64 index is hashed; validity is the gather's business.  Needs no rollout.
+ * count == 0 is a no-op.  MWB_EINVAL: a null handle or argument, a window outside the limits, count < 0, offsets_dev misaligned. */
+int mwb_rollout_window_offsets(mwb_handle *h, const struct mwb_rollout_window *w, uint64_t seed, uint64_t call,
+                               const int64_t *index_dev, int count, int32_t *offsets_dev, void *stream);
+/* replaces: obs_batch of storage.py:121 followed by the trainer's augmentation (above).  mwb_rollout_gather with the window
+ * applied on the way: row i of out_dev is [nstack * C][out_w][out_h].  offsets_dev: device int32 [count][2], 8-byte aligned, read
+ * on the device and clamped to the window's ranges there - the caller's own (UCB-DrAC, a sampler of its own) or
+ * mwb_rollout_window_offsets'.  dtype, out_dev's alignment, the index rule, zeros + mwb_rollout_rejected for rows out of range
+ * (no address is formed from such an index, nor from an unclamped offset), count == 0: all as mwb_rollout_gather.
+ * MWB_EINVAL: a null handle or argument, a window outside the limits, a bad dtype (uint8 from a grey ring included), count < 0, a
+ * misaligned out_dev / offsets_dev.  MWB_ESTATE: before mwb_rollout_enable, or before the first push. */
+int mwb_rollout_gather_window(mwb_handle *h, const int64_t *index_dev, int count, const struct mwb_rollout_window *w,
+                              const int32_t *offsets_dev, void *out_dev, int dtype, void *stream);
+
 /* ---- rollout storage, the learner half: small columns, returns / GAE scan, minibatch columns -------- */
 /* replaces: the rest of RolloutStorage (storage.py:15-18,32-34): actions, action_log_probs, value_preds, returns, psi_returns -
  * and what no reference array holds: `taken`, the sub-steps every transition took (mwb_step_repeat), by which the scans below
