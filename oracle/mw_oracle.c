@@ -241,6 +241,9 @@ struct MwoEnv {
     double cam_height, cam_fwd_disp, cam_pitch, cam_fov_y;
     double sky_color[3], light_pos[3], light_color[3], light_ambient[3];
     double max_forward_step;
+    /* test instrumentation (mwo_place_stats): iterations of place_entity_in's loop; nothing above reads these */
+    long long pl_attempts, pl_step_attempts;
+    int pl_resets, pl_in_reset, pl_cur_reset, pl_max_place, pl_max_reset, pl_step_places, pl_max_step_place;
 };
 
 static void fail(const char *msg) {
@@ -684,7 +687,9 @@ static int point_inside(const Room *r, const double *p) {
 static void place_entity_in(MwoEnv *e, Ent *ent, int room, int has_dir, double dir, double min_x, double max_x, double min_z, double max_z) {
     if (e->n_rooms <= 0) fail("create rooms before calling place_entity");
     if (!e->static_done) gen_static_data(e);
+    int attempts = 0;
     for (;;) {
+        attempts++;
         Room *r = room >= 0 ? &e->rooms[room] : &e->rooms[rs_choice_cdf(&e->rng, e->room_cdf, e->n_rooms)];
         double lx = min_x == NOVAL ? r->min_x : min_x, hx = max_x == NOVAL ? r->max_x : max_x;
         double lz = min_z == NOVAL ? r->min_z : min_z, hz = max_z == NOVAL ? r->max_z : max_z;
@@ -698,6 +703,13 @@ static void place_entity_in(MwoEnv *e, Ent *ent, int room, int has_dir, double d
         memcpy(ent->pos, pos, sizeof(pos));
         ent->dir = d;
         break;
+    }
+    e->pl_attempts += attempts;
+    if (attempts > e->pl_max_place) e->pl_max_place = attempts;
+    if (e->pl_in_reset) e->pl_cur_reset += attempts;
+    else {   /* a placement of step(): the CollectHealth respawn */
+        e->pl_step_attempts += attempts; e->pl_step_places++;
+        if (attempts > e->pl_max_step_place) e->pl_max_step_place = attempts;
     }
     e->order[e->n_order++] = ent == &e->agent ? AGENT_SLOT : (int)(ent - e->boxes);   /* self.entities.append(ent) */
 }
@@ -1065,7 +1077,10 @@ void mwo_reset(MwoEnv *e) {
     if (e->task == MWO_TMAZE_TWOBOX) e->box_base[1] = 0;          /* blue, tmaze.py:168 */
     else if (e->task == MWO_SIM2REAL_PUSH) e->box_base[1] = 5;    /* yellow, simtorealpush.py:93 */
     else if (e->task == MWO_PUTNEXT) for (int b = 0; b < 6; b++) e->box_base[b] = b;   /* for color in COLOR_NAMES, putnext.py:31 */
+    e->pl_in_reset = 1; e->pl_cur_reset = 0;
     gen_world(e);
+    e->pl_in_reset = 0; e->pl_resets++;
+    if (e->pl_cur_reset > e->pl_max_reset) e->pl_max_reset = e->pl_cur_reset;
     int dr = e->domain_rand;
     sample_param(e, dr, MWO_P_SKY_COLOR, e->sky_color);
     sample_param(e, dr, MWO_P_LIGHT_POS, e->light_pos);
@@ -1339,6 +1354,15 @@ void mwo_set_counters(MwoEnv *e, long long episode_count, long long task_step_co
 
 void mwo_set_agent(MwoEnv *e, double x, double z, double dir) { e->agent.pos[0] = x; e->agent.pos[1] = 0; e->agent.pos[2] = z; e->agent.dir = dir; }
 void mwo_set_step_count(MwoEnv *e, int sc) { e->step_count = sc; }
+
+void mwo_place_stats(MwoEnv *e, long long *out8, int clear) {
+    out8[0] = e->pl_attempts; out8[1] = e->pl_resets; out8[2] = e->pl_max_place; out8[3] = e->pl_max_reset;
+    out8[4] = e->pl_step_attempts; out8[5] = e->pl_step_places; out8[6] = e->pl_max_step_place; out8[7] = 0;
+    if (clear) {
+        e->pl_attempts = e->pl_step_attempts = 0;
+        e->pl_resets = e->pl_cur_reset = e->pl_max_place = e->pl_max_reset = e->pl_step_places = e->pl_max_step_place = 0;
+    }
+}
 void mwo_set_box(MwoEnv *e, int b, double x, double z, double dir) {
     Ent *t = &e->boxes[b];
     t->pos[0] = x; t->pos[1] = 0; t->pos[2] = z; t->dir = dir;

@@ -110,6 +110,10 @@ int mwo_set_mesh_dims(int geom, double height, double scale, double radius, int 
 void mwo_get_state(MwoEnv *e, MwoState *out);
 void mwo_set_agent(MwoEnv *e, double x, double z, double dir); /* test hook */
 void mwo_set_step_count(MwoEnv *e, int step_count);
+/* test instrumentation: iterations of place_entity's `while True` (miniworld.py:875-905) since creation or the last clear.
+ * out8 = {all attempts, reset() calls, largest single placement, largest single reset(), attempts of placements made by step()
+ * (the CollectHealth respawn), such placements, the largest of them, 0}; clear != 0 zeroes the counts after reading */
+void mwo_place_stats(MwoEnv *e, long long *out8, int clear);
 void mwo_set_box(MwoEnv *e, int box /* index in the entity list */, double x, double z, double dir); /* test hook */
 void mwo_set_box_y(MwoEnv *e, int box, double y);
 void mwo_set_carrying(MwoEnv *e, int box /* or -1 */);

@@ -94,6 +94,7 @@ def lib():
         L.mwo_get_state.argtypes = [vp, ctypes.POINTER(MwoState)]
         L.mwo_set_agent.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
         L.mwo_set_step_count.argtypes = [vp, ctypes.c_int]
+        L.mwo_place_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
         L.mwo_set_box.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double]
         L.mwo_set_box_y.argtypes = [vp, ctypes.c_int, ctypes.c_double]
         L.mwo_set_carrying.argtypes = [vp, ctypes.c_int]
@@ -340,6 +341,14 @@ class OracleEnv:
 
     def set_step_count(self, n):
         self.L.mwo_set_step_count(self.h, n)
+
+    def place_stats(self, clear=False):
+        """iterations of place_entity's loop since creation / the last clear: all of them, reset() calls, the largest single
+        placement, the largest single reset(), and the same three for the placements step() made (the CollectHealth respawn)"""
+        out = (ctypes.c_longlong * 8)()
+        self.L.mwo_place_stats(self.h, out, int(bool(clear)))
+        keys = ("attempts", "resets", "max_placement", "max_reset", "step_attempts", "step_placements", "max_step_placement")
+        return dict(zip(keys, (int(v) for v in out)))
 
     def set_counters(self, episode_count, task_step_count, goal_idx):
         self.L.mwo_set_counters(self.h, int(episode_count), int(task_step_count), int(goal_idx))
