@@ -64,12 +64,28 @@ class MwbOutputs(ctypes.Structure):
     ]
 
 
+# The fields of struct mwb_state in its order, each once (csrc/mwb_state_fields.h is the library's list; tests/test_state_fields_host.py
+# holds the two together): name, dtype, shape after [count] ("B" = mwb_num_boxes(h) slots, "B+1" = the entity list with the
+# agent), writable through mwb_set_state, exists for the entity-list tasks only.  MwbState, BatchedMiniWorld.get_state and
+# set_state are derived from it.
+STATE_FIELDS = [
+    ("agent_pos", "f8", (3,), True, False), ("agent_dir", "f8", (), True, False),
+    ("box_pos", "f8", ("B", 3), True, False), ("box_dir", "f8", ("B",), True, False), ("box_color", "f8", ("B", 3), True, False),
+    ("box_size", "f8", ("B",), True, False),
+    ("cam", "f8", (4,), True, False), ("sky_color", "f8", (3,), True, False), ("light_pos", "f8", (3,), True, False),
+    ("light_color", "f8", (3,), True, False), ("light_ambient", "f8", (3,), True, False),
+    ("step_count", "i4", (), True, False), ("rng_pos", "i4", (), False, False), ("rng_keysum", "u4", (), False, False),
+    ("n_rooms", "i4", (), False, False), ("n_segs", "i4", (), False, False),
+    ("goal_idx", "i4", (), True, False), ("episode_count", "i8", (), True, False), ("task_step_count", "i8", (), True, False),
+    ("goal_dist", "f8", (), True, False), ("rng_state", "u4", (MT_WORDS,), True, False), ("carrying", "i4", (), True, False),
+    ("ent_meta", "i4", ("B",), True, True), ("ent_radius", "f8", ("B",), False, True), ("ent_height", "f8", ("B",), False, True),
+    ("ent_scale", "f8", ("B",), False, True), ("ent_order", "i4", ("B+1",), True, True),
+    ("task_f", "f8", (), True, True), ("task_i", "i4", (), True, True), ("text_tex", "i4", (8,), False, True),
+]
+
+
 class MwbState(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in (
-        "agent_pos", "agent_dir", "box_pos", "box_dir", "box_color", "box_size", "cam", "sky_color", "light_pos",
-        "light_color", "light_ambient", "step_count", "rng_pos", "rng_keysum", "n_rooms", "n_segs",
-        "goal_idx", "episode_count", "task_step_count", "goal_dist", "rng_state", "carrying",
-        "ent_meta", "ent_radius", "ent_height", "ent_scale", "ent_order", "task_f", "task_i", "text_tex")]
+    _fields_ = [(f[0], ctypes.c_void_p) for f in STATE_FIELDS]
 
 
 class MwbRolloutInfo(ctypes.Structure):   # struct mwb_rollout_info

@@ -5,6 +5,7 @@ device tensors for actions / zero-copy views of the library's output buffers, an
 stream.  All simulation and rendering runs in the HIP kernels of csrc/.
 """
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -290,7 +291,7 @@ class Rollout:
         self.num_steps, self.nstack, self.grey, self.num_envs = int(info.num_steps), int(info.nstack), bool(info.grey), N
         self.channels = self.nstack * (1 if self.grey else 3)
         self.nbytes = int(info.ring_bytes + info.reward_bytes + info.mask_bytes + info.feature_bytes + info.age_bytes)
-        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, batch), device=batch.device)  # noqa: E731
+        as_t = functools.partial(_dev_tensor, batch)
         T = self.num_steps
         self.rewards = as_t(info.reward, (T, N), "<f4")
         self.masks = as_t(info.mask, (T + 1, N), "<f4")
@@ -308,7 +309,7 @@ class Rollout:
         _lib.check(self.L.mwb_rollout_learner_enable(b.h))
         info = _lib.MwbRolloutLearnerInfo()
         _lib.check(self.L.mwb_rollout_learner_info(b.h, ctypes.byref(info)))
-        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, b), device=b.device)  # noqa: E731
+        as_t = functools.partial(_dev_tensor, b)
         T, N = self.num_steps, self.num_envs
         self.actions = as_t(info.action, (T, N), "<i8")
         self.action_log_probs = as_t(info.log_prob, (T, N), "<f4")
@@ -563,7 +564,7 @@ class Monitor:
         _lib.check(self.L.mwb_monitor_info(batch.h, ctypes.byref(info)))
         N, C, Q = int(info.num_envs), int(info.capacity), int(info.quota_max)
         self.num_envs, self.capacity, self.quota_max = N, C, Q
-        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, batch), device=batch.device)  # noqa: E731
+        as_t = functools.partial(_dev_tensor, batch)
         for name in ("run_return", "last_return"):
             setattr(self, name, as_t(getattr(info, name), (N,), "<f8"))
         for name in ("run_len", "run_calls", "last_len", "last_calls", "finished"):
@@ -699,7 +700,7 @@ class Terminal:
         _lib.check(self.L.mwb_terminal_info(batch.h, ctypes.byref(info)))
         N, W, H, K = batch.num_envs, batch.W, batch.H, int(info.capacity)
         self.num_envs, self.capacity, self.nstack, self.channels = N, K, int(info.nstack), int(info.planes)
-        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, batch), device=batch.device)  # noqa: E731
+        as_t = functools.partial(_dev_tensor, batch)
         hwc = batch.layout == "HWC"
         self.cause = as_t(info.cause, (N,), "|u1")
         self.frames = as_t(info.frames, (N, H, W, 3) if hwc else (N, 3, W, H), "|u1")
@@ -820,7 +821,7 @@ class Levels:
         info = _lib.MwbLevelsInfo()
         _lib.check(self.L.mwb_levels_info(batch.h, ctypes.byref(info)))
         N, nl = batch.num_envs, self.num_levels
-        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, batch), device=batch.device)  # noqa: E731
+        as_t = functools.partial(_dev_tensor, batch)
         self.index, self.prev_index = as_t(info.index, (N,), "<i4"), as_t(info.prev_index, (N,), "<i4")
         self.next_level, self.episode_no = as_t(info.next_level, (N,), "<i4"), as_t(info.episode_no, (N,), "<i8")
         self.index_pair = as_t(info.index, (2, N), "<i4")   # index | prev_index are one allocation: a VecEnv's host mirror is one copy
@@ -879,6 +880,11 @@ class _DevView:
         self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
                                          "version": 2, "strides": None}
         self._owner = owner   # keeps the handle alive while views exist
+
+
+def _dev_tensor(owner, ptr, shape, typestr):
+    """Zero-copy torch view of a library-owned device buffer of the BatchedMiniWorld `owner` (which the view keeps alive)."""
+    return owner.torch.as_tensor(_DevView(ptr, shape, typestr, owner), device=owner.device)
 
 
 class BatchedMiniWorld:
@@ -962,7 +968,7 @@ class BatchedMiniWorld:
         _lib.check(self.L.mwb_get_outputs(self.h, ctypes.byref(out)))
         N, W, H = self.num_envs, self.W, self.H
         obs_shape = (N, H, W, 3) if layout == "HWC" else (N, 3, W, H)
-        as_t = lambda ptr, shape, ts: torch.as_tensor(_DevView(ptr, shape, ts, self), device=self.device)  # noqa: E731
+        as_t = functools.partial(_dev_tensor, self)
         self.obs = as_t(out.obs, obs_shape, "|u1")
         self.depth = as_t(out.depth, (N, H, W, 1), "<f4") if self.want_depth else None
         # GreyscaleWrapper's observation as float32 (wrappers.py:29-45 + .float()): [N,H,W,1], or [N,1,W,H] transposed; zero-copy
@@ -1227,12 +1233,9 @@ class BatchedMiniWorld:
         """Synchronous: raises if world generation ever flagged a failure (see mwb_check)."""
         _lib.check(self.L.mwb_check(self.h))
 
-    _STATE_F64 = {"agent_pos": (3,), "agent_dir": (), "cam": (4,), "sky_color": (3,), "light_pos": (3,),
-                  "light_color": (3,), "light_ambient": (3,), "goal_dist": ()}
-    _STATE_BOX = {"box_pos": (3,), "box_dir": (), "box_color": (3,), "box_size": ()}   # [count][B] + shape
-    _STATE_INT = {"step_count": np.int32, "rng_pos": np.int32, "rng_keysum": np.uint32, "n_rooms": np.int32,
-                  "n_segs": np.int32, "goal_idx": np.int32, "episode_count": np.int64, "task_step_count": np.int64,
-                  "carrying": np.int32}
+    def _state_shape(self, shape):
+        """the shape of a row of _lib.STATE_FIELDS after [count], for this batch's B"""
+        return tuple({"B": self.n_boxes, "B+1": self.n_boxes + 1}.get(s, s) for s in shape)
 
     def get_state(self, first=0, count=None, rng_state=False):
         """Host snapshot of the env range (mwb_get_state).  Box fields come as "boxes_pos" [count, B, 3],
@@ -1240,58 +1243,40 @@ class BatchedMiniWorld:
         reference's attribute names: "box_*" = entity 0 (env.box / red_box), "box2_*" = entity 1."""
         self.check()
         count = self.num_envs - first if count is None else count
-        B = self.n_boxes
-        out = {k: np.zeros((count,) + s, np.float64) for k, s in self._STATE_F64.items()}
-        boxes = {k: np.zeros((count, B) + s, np.float64) for k, s in self._STATE_BOX.items()}
-        out.update({k: np.zeros(count, dt) for k, dt in self._STATE_INT.items()})
-        if rng_state:
-            out["rng_state"] = np.zeros((count, _lib.MT_WORDS), np.uint32)
+        # every field of the table; the general entity list (per slot kind / flags / dimensions, the list order, the task's
+        # counters) for the entity tasks only, the 625 words per env of the generator on request
+        arrays = {name: np.zeros((count,) + self._state_shape(shape), dt) for name, dt, shape, _, ent in _lib.STATE_FIELDS
+                  if (self.ent_task or not ent) and (rng_state or name != "rng_state")}
         st = _lib.MwbState()
-        for k, v in list(out.items()) + list(boxes.items()):
+        for k, v in arrays.items():
             setattr(st, k, v.ctypes.data_as(ctypes.c_void_p))
-        ents = {}
-        if self.ent_task:   # the general entity list: per slot kind / flags / dimensions, the list order, the task's counters
-            ents = {"ent_meta": np.zeros((count, B), np.int32), "ent_radius": np.zeros((count, B)), "ent_height": np.zeros((count, B)),
-                    "ent_scale": np.zeros((count, B)), "ent_order": np.zeros((count, B + 1), np.int32), "task_f": np.zeros(count),
-                    "task_i": np.zeros(count, np.int32), "text_tex": np.zeros((count, 8), np.int32)}
-            for k, v in ents.items():
-                setattr(st, k, v.ctypes.data_as(ctypes.c_void_p))
         _lib.check(self.L.mwb_get_state(self.h, first, count, ctypes.byref(st)))
+        out = {k: v for k, v in arrays.items() if not k.startswith("box_")}
         if self.ent_task:
-            m = ents["ent_meta"]
-            ents.update({"ent_kind": m & 15, "ent_geom": (m >> 4) & 15, "ent_static": (m >> 8) & 1, "ent_alive": (m >> 9) & 1,
-                         "ent_rad_f32": (m >> 10) & 1, "ent_color": ((m >> 12) & 15) - 1})
-        out.update(ents)
-        for k, v in boxes.items():
-            out["boxes_" + k[4:]] = v
-            out[k] = v[:, 0]
-            out["box2_" + k[4:]] = v[:, 1] if B > 1 else np.zeros_like(v[:, 0])
+            m = out["ent_meta"]
+            out.update({"ent_kind": m & 15, "ent_geom": (m >> 4) & 15, "ent_static": (m >> 8) & 1, "ent_alive": (m >> 9) & 1,
+                        "ent_rad_f32": (m >> 10) & 1, "ent_color": ((m >> 12) & 15) - 1})
+        for k, v in arrays.items():
+            if k.startswith("box_"):
+                out["boxes_" + k[4:]] = v
+                out[k] = v[:, 0]
+                out["box2_" + k[4:]] = v[:, 1] if self.n_boxes > 1 else np.zeros_like(v[:, 0])
         return out
 
     def set_state(self, first, **fields):
         """Overwrite simulator state of envs first .. first+count-1 (mwb_set_state).  Keys as returned by
         get_state(): agent_pos [count,3], agent_dir, boxes_pos [count,B,3], boxes_dir, boxes_color, boxes_size,
         cam, sky_color, light_*, step_count, goal_idx, episode_count, task_step_count, goal_dist, carrying,
-        rng_state [count,625]."""
+        rng_state [count,625]; for the entity tasks also ent_meta (the alive bit), ent_order, task_f, task_i."""
+        writable = {name: (dt, shape) for name, dt, shape, w, _ in _lib.STATE_FIELDS if w}
         st = _lib.MwbState()
         keep, count = [], None
         for k, v in fields.items():
             name = "box_" + k[6:] if k.startswith("boxes_") else k
-            if name in self._STATE_BOX:
-                shape, dt = (-1, self.n_boxes) + self._STATE_BOX[name], np.float64
-            elif name in self._STATE_F64:
-                shape, dt = (-1,) + self._STATE_F64[name], np.float64
-            elif name == "rng_state":
-                shape, dt = (-1, _lib.MT_WORDS), np.uint32
-            elif name in ("step_count", "goal_idx", "episode_count", "task_step_count", "carrying"):
-                shape, dt = (-1,), self._STATE_INT[name]
-            elif name in ("ent_meta", "ent_order", "task_i"):
-                shape, dt = {"ent_meta": (-1, self.n_boxes), "ent_order": (-1, self.n_boxes + 1), "task_i": (-1,)}[name], np.int32
-            elif name == "task_f":
-                shape, dt = (-1,), np.float64
-            else:
+            if name not in writable:
                 raise KeyError("set_state: %r is not a writable state field" % k)
-            a = np.ascontiguousarray(np.asarray(v, dtype=dt).reshape(shape))
+            dt, shape = writable[name]
+            a = np.ascontiguousarray(np.asarray(v, dtype=dt).reshape((-1,) + self._state_shape(shape)))
             if count is not None and a.shape[0] != count:
                 raise ValueError("set_state: fields disagree on the number of envs")
             count = a.shape[0]
@@ -1366,7 +1351,7 @@ class BatchedMiniWorld:
         self._stack_args = dict(nstack=nstack, dtype=dtype, sliding=sliding, fused=fused, grey=grey)
         self._stack_c, self._stack_sliding = nstack * (1 if grey else 3), bool(sliding)
         shape = (self.num_envs, planes.value, self.W, self.H)
-        self._stack_base = torch.as_tensor(_DevView(out.stack, shape, "<f4" if is_f else "|u1", self), device=self.device)
+        self._stack_base = _dev_tensor(self, out.stack, shape, "<f4" if is_f else "|u1")
         self.stack = self._stack_base[:, first.value:first.value + self._stack_c]
         return self.stack
 

@@ -10,7 +10,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["mwb_api.hip", "mwb_kernels.hip", "mwb_copy.hip", "mwb_repeat.hip", "mwb_rollout.hip", "mwb_rollout_window.hip", "mwb_rollout_learner.hip", "mwb_monitor.hip", "mwb_terminal.hip", "mwb_levels.hip"]
-HEADERS = ["mwb_internal.h", "mwb_task_table.h", "mwb_copy_check.h", "mwb_repeat_fold.h", "mwb_rollout_map.h", "mwb_rollout_window_map.h", "mwb_returns_scan.h", "mwb_monitor_map.h", "mwb_terminal_map.h", "mwb_levels_map.h", "mwb_dispatch_map.h", "mwb_seg_groups.h", "mwb_lds_layout.h", "mwb_glibc_trig.h", "mwb_sincos_table.inc", "mwb_texture_host.h", os.path.join("..", "..", "include", "miniworld_batch.h")]
+HEADERS = ["mwb_internal.h", "mwb_alloc_list.h", "mwb_state_fields.h", "mwb_task_table.h", "mwb_copy_check.h", "mwb_repeat_fold.h", "mwb_rollout_map.h", "mwb_rollout_window_map.h", "mwb_returns_scan.h", "mwb_monitor_map.h", "mwb_terminal_map.h", "mwb_levels_map.h", "mwb_dispatch_map.h", "mwb_seg_groups.h", "mwb_lds_layout.h", "mwb_glibc_trig.h", "mwb_sincos_table.inc", "mwb_texture_host.h", os.path.join("..", "..", "include", "miniworld_batch.h")]
 OUT = os.path.join(HERE, "libmwbatch.so")
 # hipcc's per-kernel resource remarks of the build that produced OUT, headed by a digest of the sources: tests/test_kernel_budget.py
 # reads them instead of compiling the kernels a second time (five minutes) when the digest still matches

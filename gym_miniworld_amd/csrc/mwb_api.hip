@@ -15,6 +15,8 @@
 #include <vector>
 
 #include "mwb_internal.h"
+#include "mwb_alloc_list.h"
+#include "mwb_state_fields.h"
 #include "mwb_lds_layout.h"
 #include "mwb_rollout_map.h"
 #include "mwb_rollout_window_map.h"
@@ -55,13 +57,21 @@ struct DevGuard {
     if (_dev_guard.err != hipSuccess)                                                                \
         return set_err(MWB_EHIP, std::string("hipSetDevice: ") + hipGetErrorString(_dev_guard.err))
 
+// The opening of an entry point that needs a feature: MWB_EINVAL unless `ok` (the handle and the pointers that must not be null;
+// missing = "handle" or "argument"), MWB_ESTATE until the feature's enable function has run
+#define NEED(ok, missing, on, enable)                                                                       \
+    do {                                                                                                    \
+        if (!(ok)) return set_err(MWB_EINVAL, std::string(__func__) + ": null " missing);                    \
+        if (!(on)) return set_err(MWB_ESTATE, std::string(__func__) + ": call " #enable " first");           \
+    } while (0)
+
 struct mwb_handle {
     mwb_config cfg = {};
     MwbDev dev = {};
-    std::vector<void *> allocs;
+    MwbAllocList mem;   // every device allocation of the handle (dev_alloc); mwb_destroy frees from here and nowhere else
     std::vector<std::vector<uint32_t>> tex_levels[MWB_MAX_TEX];   // host mip chains (RGBA8 packed)
     int tex_w[MWB_MAX_TEX] = {}, tex_h[MWB_MAX_TEX] = {};
-    uint32_t *texels_dev = nullptr;
+    uint32_t *texels_dev = nullptr;   // replaced by every upload_textures
     MwbTexDesc *tex_desc_dev = nullptr;
     bool seeded = false, textures_dirty = false, have_textures = false;
     bool have_obs = false;   // some pass has rendered an observation since creation
@@ -90,7 +100,7 @@ struct mwb_handle {
     struct HostMesh { bool set = false; int n_tris = 0, n_nodes = 0, n_orders = 1, tex_id = -1; float min_c[3], max_c[3]; std::vector<float> nodes, tris, tris2, shade; };
     HostMesh meshes[MWB_NUM_MESHES];
     bool meshes_dirty = false;
-    float4 *mesh_data_dev = nullptr;
+    float4 *mesh_data_dev = nullptr;   // replaced by every upload_meshes
     MwbMeshDesc *mesh_desc_dev = nullptr;
     float *view_frame = nullptr;   // frame constants of mwb_render_view's size (lazily allocated)
     bool bulk_fixed = false;     // a step's bulk launch takes render_fixed_kernel (mwb_bulk_fixed_ok at creation and not MWB_NO_FIXED=1); grey output still overrides
@@ -111,7 +121,7 @@ struct mwb_handle {
     double *rep_sum = nullptr;          // [N] float64 sum of the call's sub-step rewards
     int32_t *rep_taken = nullptr;       // [N] sub-steps taken in the last call (mwb_repeat_taken)
     uint8_t *rep_same = nullptr, *rep_frozen = nullptr;   // [N] each: every sub-step so far left the frame standing / the env takes no further sub-step
-    // ---- the rollout storage (mwb_rollout_enable): its own allocations (not in `allocs`: a failed enable frees what it got)
+    // ---- the rollout storage (mwb_rollout_enable)
     bool rollout_on = false;
     MwbRollout rollout = {};
     size_t rollout_ring_bytes = 0;
@@ -119,17 +129,16 @@ struct mwb_handle {
     bool learner_on = false;
     MwbLearner learner = {};
     bool last_pass_repeat = false;      // the last pass on the handle was an mwb_step_repeat: a push records its `taken` buffer
-    // ---- the episode monitor (mwb_monitor_enable): one allocation of its own, carved into the arrays of `monitor`
+    // ---- the episode monitor (mwb_monitor_enable): one allocation, carved into the arrays of `monitor`
     bool monitor_on = false;
     MwbMonitor monitor = {};
-    void *monitor_mem = nullptr;
     void *monitor_pack = nullptr;       // last_return | last_len | last_calls | counts | logged | retired, contiguous
     size_t monitor_pack_bytes = 0;
-    // ---- terminal observations (mwb_terminal_enable): its buffers are in `allocs`; dev.end_cause is terminal.cause
+    // ---- terminal observations (mwb_terminal_enable); dev.end_cause is terminal.cause
     bool terminal_on = false;
     MwbTerminal terminal = {};
     size_t terminal_rows_bytes = 0;
-    // ---- level sets (mwb_levels_enable): its buffers are in `allocs`; mode and sampler seed as the host set them last
+    // ---- level sets (mwb_levels_enable); mode and sampler seed as the host set them last
     bool levels_on = false;
     MwbLevels levels = {};
     int levels_mode = 0;
@@ -150,6 +159,7 @@ extern "C" int mwb_abi_version(void) { return MWB_ABI_VERSION; }
 extern "C" int mwb_seed_key(uint64_t seed, uint32_t key[2]) { return mwb_levels_seed_key(seed, key); }
 
 // ------------------------------------------------------------------------------------ helpers
+// n zeroed elements, owned by the handle's allocation list (mwb_alloc_list.h).  The caller holds the device guard.
 template <typename T>
 static int dev_alloc(mwb_handle *h, T **p, size_t n) {
     void *q = nullptr;
@@ -157,11 +167,28 @@ static int dev_alloc(mwb_handle *h, T **p, size_t n) {
     hipError_t e = hipMalloc(&q, bytes);
     if (e != hipSuccess) return set_err(MWB_ENOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
     e = hipMemset(q, 0, bytes);
-    if (e != hipSuccess) return set_err(MWB_EHIP, std::string("hipMemset failed: ") + hipGetErrorString(e));
-    h->allocs.push_back(q);
+    if (e != hipSuccess) { (void)hipFree(q); return set_err(MWB_EHIP, std::string("hipMemset failed: ") + hipGetErrorString(e)); }
+    h->mem.add(q);
     *p = (T *)q;
     return MWB_OK;
 }
+static void dev_free(void *p) { (void)hipFree(p); }
+// A buffer that is replaced during the handle's life: the old one goes (hipFree waits for the kernels still reading it)
+template <typename T>
+static int dev_realloc(mwb_handle *h, T **p, size_t n) {
+    h->mem.release(*p, dev_free);
+    *p = nullptr;
+    return dev_alloc(h, p, n);
+}
+// What a feature allocates while it is being enabled: freed again unless the enable reaches keep().  Declared after the device
+// guard, so that it frees on the handle's device.  A refused or failed enable leaves the handle as it was.
+struct AllocScope {
+    mwb_handle *h;
+    size_t mark;
+    explicit AllocScope(mwb_handle *handle) : h(handle), mark(handle->mem.mark()) {}
+    ~AllocScope() { if (h) h->mem.release_to(mark, dev_free); }
+    void keep() { h = nullptr; }
+};
 
 static void default_params(double p[MWB_NPARAM][9]) {   // params.py:110-123
     static const double T[MWB_NPARAM][9] = {
@@ -305,28 +332,11 @@ extern "C" int mwb_create(const mwb_config *cfg, mwb_handle **out) {
     return MWB_OK;
 }
 
-static void rollout_free(MwbRollout &r) {
-    void *ps[] = {r.ring, r.age, r.reward, r.mask, r.feature, r.rejected};
-    for (void *p : ps) if (p) hipFree(p);
-    r = MwbRollout{};
-}
-static void learner_free(MwbLearner &l) {
-    void *ps[] = {l.action, l.log_prob, l.value, l.taken, l.ret, l.adv, l.psi_ret};
-    for (void *p : ps) if (p) hipFree(p);
-    l = MwbLearner{};
-}
-
 extern "C" int mwb_destroy(mwb_handle *h) {
     if (!h) return MWB_OK;
     DevGuard _dev_guard(h->cfg.device);
     hipDeviceSynchronize();
-    for (void *p : h->allocs) hipFree(p);
-    if (h->texels_dev) hipFree(h->texels_dev);
-    if (h->mesh_data_dev) hipFree(h->mesh_data_dev);
-    if (h->copy_pairs) hipFree(h->copy_pairs);
-    rollout_free(h->rollout);
-    learner_free(h->learner);
-    if (h->monitor_mem) hipFree(h->monitor_mem);
+    h->mem.release_to(0, dev_free);
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->ev_join) hipEventDestroy(h->ev_join);
@@ -372,8 +382,7 @@ static int upload_textures(mwb_handle *h) {
         append_pyramid_footprints(h->tex_levels[i], h->tex_w[i], h->tex_h[i], desc[i].level_off, all);
     }
     HIP_TRY(hipDeviceSynchronize());
-    if (h->texels_dev) { hipFree(h->texels_dev); h->texels_dev = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->texels_dev, all.size() * 4));
+    if (int rc = dev_realloc(h, &h->texels_dev, all.size())) return rc;
     HIP_TRY(hipMemcpy(h->texels_dev, all.data(), all.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->tex_desc_dev, desc, sizeof(desc), hipMemcpyHostToDevice));
     h->dev.texels = h->texels_dev;
@@ -459,8 +468,7 @@ static int upload_meshes(mwb_handle *h) {   // the caller holds the device guard
         desc[g].shade_off = (uint32_t)(all.size() / 4); all.insert(all.end(), m.shade.begin(), m.shade.end());
     }
     HIP_TRY(hipDeviceSynchronize());
-    if (h->mesh_data_dev) { hipFree(h->mesh_data_dev); h->mesh_data_dev = nullptr; }
-    HIP_TRY(hipMalloc((void **)&h->mesh_data_dev, (all.size() ? all.size() : 4) * sizeof(float)));
+    if (int rc = dev_realloc(h, &h->mesh_data_dev, (all.size() + 3) / 4)) return rc;
     if (!all.empty()) HIP_TRY(hipMemcpy(h->mesh_data_dev, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->mesh_desc_dev, desc, sizeof(desc), hipMemcpyHostToDevice));
     h->dev.mesh_data = h->mesh_data_dev;
@@ -474,6 +482,17 @@ static int upload_meshes(mwb_handle *h) {   // the caller holds the device guard
 static int invalidate_frames(mwb_handle *h, int first, int count) {
     if (!h->dev.frame_cached || count <= 0) return MWB_OK;
     HIP_TRY(hipMemset(h->dev.frame_cached + first, 0, (size_t)count));
+    HIP_TRY(hipDeviceSynchronize());
+    return MWB_OK;
+}
+
+// The counters kernels add to and the host reads: n of them to `out`, then (clear) zero again.  Synchronous.
+static int read_counters(mwb_handle *h, unsigned long long *out, unsigned long long *counters_dev, size_t n, bool clear = true) {
+    USE_DEVICE(h->cfg.device);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, counters_dev, n * sizeof(*out), hipMemcpyDeviceToHost));
+    if (!clear) return MWB_OK;
+    HIP_TRY(hipMemset(counters_dev, 0, n * sizeof(*out)));
     HIP_TRY(hipDeviceSynchronize());
     return MWB_OK;
 }
@@ -718,6 +737,12 @@ extern "C" int mwb_render(mwb_handle *h, void *stream) {
     return render_tail(h, 0, s);
 }
 
+// Frame constants of a view that is not the observation, kept apart from the observation's; the first such view allocates them
+// (one dev_alloc: a failure leaves the handle as it was).  The caller holds the device guard.
+static int ensure_view_frame(mwb_handle *h) {
+    return h->view_frame ? MWB_OK : dev_alloc(h, &h->view_frame, (size_t)h->dev.N * h->dev.frame_words);
+}
+
 extern "C" int mwb_render_top_view(mwb_handle *h, uint8_t *out_dev, int width, int height, void *stream) {
     if (!h || !out_dev) return set_err(MWB_EINVAL, "mwb_render_top_view: null argument");
     if (width < 1 || height < 1 || width > 4096 || height > 4096) return set_err(MWB_EINVAL, "mwb_render_top_view: bad frame size");
@@ -726,9 +751,7 @@ extern "C" int mwb_render_top_view(mwb_handle *h, uint8_t *out_dev, int width, i
     hipStream_t s = (hipStream_t)stream;
     if (h->dev.ent_task) {   // the current entity list (step_pass 0, as mwb_render), prepared into the view's own frame constants:
         // the observation's are left as they are, so no later observation, reward or done depends on this call
-        if (!h->view_frame) {
-            rc = dev_alloc(h, &h->view_frame, (size_t)h->dev.N * h->dev.frame_words); if (rc) return rc;
-        }
+        rc = ensure_view_frame(h); if (rc) return rc;
         MwbDev v = h->dev;
         v.frame = h->view_frame; v.stk = nullptr; v.step_pass = 0; v.wg_ts = nullptr;
         mwb_launch_prep(v, 0, s);
@@ -748,10 +771,7 @@ extern "C" int mwb_render_view(mwb_handle *h, uint8_t *out_dev, float *depth_dev
     USE_DEVICE(h->cfg.device);
     int rc = ensure_ready(h, false); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const size_t words = (size_t)h->dev.N * h->dev.frame_words;
-    if (!h->view_frame) {   // frame constants of the other view size, kept apart from the observation's
-        rc = dev_alloc(h, &h->view_frame, words); if (rc) return rc;
-    }
+    rc = ensure_view_frame(h); if (rc) return rc;
     MwbDev v = h->dev;
     v.W = width; v.H = height; v.layout = MWB_LAYOUT_HWC; v.obs = out_dev; v.depth = depth_dev; v.want_depth = depth_dev ? 1 : 0;
     v.frame = h->view_frame; v.stk = nullptr; v.step_pass = 0; v.wg_ts = nullptr;
@@ -808,17 +828,18 @@ extern "C" int mwb_grey_enable(mwb_handle *h) {
     // the buffer is filled by the pass that writes obs: enabled after the first one it would lack the frame already rendered
     if (h->have_obs) return set_err(MWB_ESTATE, "mwb_grey_enable: must be called before the first mwb_reset / mwb_step / mwb_render");
     USE_DEVICE(h->cfg.device);
+    AllocScope scope(h);
     float *p = nullptr;
     const size_t n = (size_t)d.N * d.W * d.H;
     int rc = dev_alloc(h, &p, n);
     if (rc) return rc;
     d.grey = p; h->grey_bytes = n * sizeof(float);
+    scope.keep();
     return MWB_OK;
 }
 
 extern "C" int mwb_grey_output(mwb_handle *h, float **grey, size_t *bytes) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_grey_output: null handle");
-    if (!h->dev.grey) return set_err(MWB_ESTATE, "mwb_grey_output: call mwb_grey_enable first");
+    NEED(h, "handle", h->dev.grey, mwb_grey_enable);
     if (grey) *grey = h->dev.grey;
     if (bytes) *bytes = h->grey_bytes;
     return MWB_OK;
@@ -860,9 +881,11 @@ extern "C" int mwb_stack_enable(mwb_handle *h, int nstack, int dtype) {
     USE_DEVICE(h->cfg.device);
     const int planes = sliding ? nstack * cpf + cpf * MWB_STACK_SLACK_FRAMES : nstack * cpf;
     size_t bytes = (size_t)d.N * planes * d.W * d.H * (dtype == 1 ? 4 : 1);
+    AllocScope scope(h);
     uint8_t *p = nullptr;
     int rc = dev_alloc(h, &p, bytes);
     if (rc) return rc;
+    scope.keep();
     h->stack = p; h->stack_n = nstack; h->stack_dtype = dtype; h->stack_bytes = bytes;
     h->stack_planes = sliding ? planes : 0; h->stack_pos = 0; h->stack_fused = fused; h->stack_cpf = cpf;
     if (fused) {
@@ -914,26 +937,22 @@ extern "C" int mwb_rollout_enable(mwb_handle *h, int num_steps, int nstack, unsi
     r.base = 0; r.cursor = -1;
     r.frame_bytes = (size_t)d.W * d.H * (grey ? sizeof(float) : 3);
     const size_t N = (size_t)d.N, T1 = (size_t)num_steps + 1, ring_bytes = (size_t)r.R * N * r.frame_bytes;
-    int rc = MWB_OK;
-    auto get = [&](auto *&p, size_t bytes) {
-        if (rc != MWB_OK) return;
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, bytes);
-        if (e != hipSuccess) { rc = set_err(MWB_ENOMEM, std::string("mwb_rollout_enable: hipMalloc failed: ") + hipGetErrorString(e)); return; }
-        p = static_cast<std::remove_reference_t<decltype(p)>>(q);
-        if ((e = hipMemset(q, 0, bytes)) != hipSuccess) rc = set_err(MWB_EHIP, std::string("mwb_rollout_enable: hipMemset failed: ") + hipGetErrorString(e));
-    };
-    get(r.ring, ring_bytes); get(r.age, T1 * N); get(r.reward, (size_t)num_steps * N * sizeof(float)); get(r.mask, T1 * N * sizeof(float));
-    get(r.feature, T1 * N * 2 * sizeof(float)); get(r.rejected, sizeof(unsigned long long));
-    if (rc == MWB_OK && hipDeviceSynchronize() != hipSuccess) rc = set_err(MWB_EHIP, "mwb_rollout_enable: hipDeviceSynchronize failed");
-    if (rc != MWB_OK) { rollout_free(r); return rc; }   // the handle is as it was
+    AllocScope scope(h);
+    int rc = dev_alloc(h, &r.ring, ring_bytes);
+    if (!rc) rc = dev_alloc(h, &r.age, T1 * N);
+    if (!rc) rc = dev_alloc(h, &r.reward, (size_t)num_steps * N);
+    if (!rc) rc = dev_alloc(h, &r.mask, T1 * N);
+    if (!rc) rc = dev_alloc(h, &r.feature, T1 * N * 2);
+    if (!rc) rc = dev_alloc(h, &r.rejected, (size_t)1);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    scope.keep();
     h->rollout = r; h->rollout_ring_bytes = ring_bytes; h->rollout_on = true;
     return MWB_OK;
 }
 
 extern "C" int mwb_rollout_push(mwb_handle *h, int after_reset, const uint8_t *fresh_dev, void *stream) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_push: null handle");
-    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_push: call mwb_rollout_enable first");
+    NEED(h, "handle", h->rollout_on, mwb_rollout_enable);
     MwbRollout &r = h->rollout;
     if (!after_reset && r.cursor < 0) return set_err(MWB_ESTATE, "mwb_rollout_push: the first push must follow a reset (after_reset != 0)");
     if (!after_reset && r.cursor >= r.T) return set_err(MWB_ESTATE, "mwb_rollout_push: the rollout holds num_steps steps already: call mwb_rollout_after_update");
@@ -956,8 +975,7 @@ extern "C" int mwb_rollout_push(mwb_handle *h, int after_reset, const uint8_t *f
 }
 
 extern "C" int mwb_rollout_gather(mwb_handle *h, const int64_t *index_dev, int count, void *out_dev, int dtype, void *stream) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_gather: null handle");
-    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_gather: call mwb_rollout_enable first");
+    NEED(h, "handle", h->rollout_on, mwb_rollout_enable);
     const MwbRollout &r = h->rollout;
     if (dtype != 0 && dtype != 1) return set_err(MWB_EINVAL, "mwb_rollout_gather: dtype must be 0 (uint8) or 1 (float32)");
     if (r.grey && dtype == 0) return set_err(MWB_EINVAL, "mwb_rollout_gather: a grey rollout is gathered as float32 (the reference defines no uint8 grey)");
@@ -997,8 +1015,7 @@ extern "C" int mwb_rollout_window_offsets(mwb_handle *h, const struct mwb_rollou
 extern "C" int mwb_rollout_gather_window(mwb_handle *h, const int64_t *index_dev, int count, const struct mwb_rollout_window *w,
                                          const int32_t *offsets_dev, void *out_dev, int dtype, void *stream) {
     if (!h) return set_err(MWB_EINVAL, "mwb_rollout_gather_window: null handle");
-    if (!w) return set_err(MWB_EINVAL, "mwb_rollout_gather_window: null argument");
-    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_gather_window: call mwb_rollout_enable first");
+    NEED(w, "argument", h->rollout_on, mwb_rollout_enable);
     const MwbRollout &r = h->rollout;
     MwbWindow win;
     if (int rc = window_of(h, w, "mwb_rollout_gather_window", win)) return rc;
@@ -1016,8 +1033,7 @@ extern "C" int mwb_rollout_gather_window(mwb_handle *h, const int64_t *index_dev
 }
 
 extern "C" int mwb_rollout_after_update(mwb_handle *h, void *stream) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_after_update: null handle");
-    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_after_update: call mwb_rollout_enable first");
+    NEED(h, "handle", h->rollout_on, mwb_rollout_enable);
     MwbRollout &r = h->rollout;
     if (r.cursor < 0) return set_err(MWB_ESTATE, "mwb_rollout_after_update: nothing has been pushed yet");
     USE_DEVICE(h->cfg.device);
@@ -1029,8 +1045,7 @@ extern "C" int mwb_rollout_after_update(mwb_handle *h, void *stream) {
 }
 
 extern "C" int mwb_rollout_info(mwb_handle *h, struct mwb_rollout_info *out) {
-    if (!h || !out) return set_err(MWB_EINVAL, "mwb_rollout_info: null argument");
-    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_info: call mwb_rollout_enable first");
+    NEED(h && out, "argument", h->rollout_on, mwb_rollout_enable);
     const MwbRollout &r = h->rollout;
     const size_t N = (size_t)r.N, T1 = (size_t)r.T + 1;
     memset(out, 0, sizeof(*out));
@@ -1042,15 +1057,9 @@ extern "C" int mwb_rollout_info(mwb_handle *h, struct mwb_rollout_info *out) {
 }
 
 extern "C" int mwb_rollout_rejected(mwb_handle *h, unsigned long long *rows) {
-    if (!h || !rows) return set_err(MWB_EINVAL, "mwb_rollout_rejected: null argument");
-    *rows = 0;
-    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_rejected: call mwb_rollout_enable first");
-    USE_DEVICE(h->cfg.device);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(rows, h->rollout.rejected, sizeof(*rows), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(h->rollout.rejected, 0, sizeof(*rows)));
-    HIP_TRY(hipDeviceSynchronize());
-    return MWB_OK;
+    if (rows) *rows = 0;
+    NEED(h && rows, "argument", h->rollout_on, mwb_rollout_enable);
+    return read_counters(h, rows, h->rollout.rejected, 1);
 }
 
 // ------------------------------------------------------------------------------------ episode monitor
@@ -1092,30 +1101,22 @@ extern "C" int mwb_monitor_enable(mwb_handle *h, int capacity, int quota_max) {
         piece(m.wave_ballot, NW * 8, false); piece(m.wave_base, NW * 4, false); piece(m.wave_aux, NW * 4, false);
     };
     carve();
-    const size_t bytes = at;
-    void *mem = nullptr;
-    hipError_t e = hipMalloc(&mem, bytes);
-    if (e != hipSuccess) return set_err(MWB_ENOMEM, std::string("mwb_monitor_enable: hipMalloc failed: ") + hipGetErrorString(e));
-    base = (char *)mem;
+    AllocScope scope(h);
+    if (int rc = dev_alloc(h, &base, at)) return rc;
     carve();
     m.counts32 = (uint32_t *)(m.counts64 + 2);
     if (!quota_max) { m.tab_return = nullptr; m.tab_len = nullptr; }
-    int rc = MWB_OK;
-    if ((e = hipMemset(mem, 0, bytes)) != hipSuccess) rc = set_err(MWB_EHIP, std::string("mwb_monitor_enable: hipMemset failed: ") + hipGetErrorString(e));
-    if (rc == MWB_OK) {   // quota 0, remaining = N, the table as NaN / -1
-        mwb_launch_monitor_quota(m, 0, nullptr);
-        rc = check_launch("monitor_quota_kernel");
-    }
-    if (rc == MWB_OK && hipDeviceSynchronize() != hipSuccess) rc = set_err(MWB_EHIP, "mwb_monitor_enable: hipDeviceSynchronize failed");
-    if (rc != MWB_OK) { hipFree(mem); return rc; }   // the handle is as it was
-    h->monitor = m; h->monitor_mem = mem; h->monitor_pack = m.last_return; h->monitor_pack_bytes = pack_bytes; h->monitor_on = true;
+    mwb_launch_monitor_quota(m, 0, nullptr);   // quota 0, remaining = N, the table as NaN / -1
+    if (int rc = check_launch("monitor_quota_kernel")) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    scope.keep();
+    h->monitor = m; h->monitor_pack = m.last_return; h->monitor_pack_bytes = pack_bytes; h->monitor_on = true;
     return MWB_OK;
 }
 
 extern "C" int mwb_monitor_update(mwb_handle *h, const uint8_t *skip_mask_dev, const double *reward64_dev, const uint8_t *done_dev,
                                   const int32_t *taken_dev, void *stream) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_monitor_update: null handle");
-    if (!h->monitor_on) return set_err(MWB_ESTATE, "mwb_monitor_update: call mwb_monitor_enable first");
+    NEED(h, "handle", h->monitor_on, mwb_monitor_enable);
     USE_DEVICE(h->cfg.device);
     // the sub-steps of the call: the repeat's count if that was the last pass, 1 (NULL) after a plain step - the rollout's rule
     const int32_t *taken = taken_dev ? taken_dev : (h->last_pass_repeat ? h->rep_taken : nullptr);
@@ -1125,16 +1126,14 @@ extern "C" int mwb_monitor_update(mwb_handle *h, const uint8_t *skip_mask_dev, c
 }
 
 extern "C" int mwb_monitor_clear(mwb_handle *h, const uint8_t *mask_dev, int partial, void *stream) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_monitor_clear: null handle");
-    if (!h->monitor_on) return set_err(MWB_ESTATE, "mwb_monitor_clear: call mwb_monitor_enable first");
+    NEED(h, "handle", h->monitor_on, mwb_monitor_enable);
     USE_DEVICE(h->cfg.device);
     mwb_launch_monitor_clear(h->monitor, mask_dev, partial != 0, (hipStream_t)stream);
     return check_launch("monitor_clear_kernel");
 }
 
 extern "C" int mwb_monitor_quota(mwb_handle *h, int quota, void *stream) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_monitor_quota: null handle");
-    if (!h->monitor_on) return set_err(MWB_ESTATE, "mwb_monitor_quota: call mwb_monitor_enable first");
+    NEED(h, "handle", h->monitor_on, mwb_monitor_enable);
     if (quota < 0 || quota > h->monitor.Q) return set_err(MWB_EINVAL, "mwb_monitor_quota: quota must lie in 0 .. quota_max = " + std::to_string(h->monitor.Q));
     USE_DEVICE(h->cfg.device);
     mwb_launch_monitor_quota(h->monitor, quota, (hipStream_t)stream);
@@ -1142,8 +1141,7 @@ extern "C" int mwb_monitor_quota(mwb_handle *h, int quota, void *stream) {
 }
 
 extern "C" int mwb_monitor_info(mwb_handle *h, struct mwb_monitor_info *out) {
-    if (!h || !out) return set_err(MWB_EINVAL, "mwb_monitor_info: null argument");
-    if (!h->monitor_on) return set_err(MWB_ESTATE, "mwb_monitor_info: call mwb_monitor_enable first");
+    NEED(h && out, "argument", h->monitor_on, mwb_monitor_enable);
     const MwbMonitor &m = h->monitor;
     memset(out, 0, sizeof(*out));
     out->run_return = m.run_return; out->last_return = m.last_return;
@@ -1172,35 +1170,29 @@ static_assert(MWB_RETURNS_MAX_K == MWB_MAX_REPEAT, "the discount tables have one
 static_assert(MWB_SCAN_DISCOUNTED == MWB_RETURNS_DISCOUNTED && MWB_SCAN_GAE == MWB_RETURNS_GAE && MWB_SCAN_PSI == MWB_RETURNS_PSI, "mode numbers");
 
 extern "C" int mwb_rollout_learner_enable(mwb_handle *h) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_learner_enable: null handle");
-    if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_learner_enable: call mwb_rollout_enable first");
+    NEED(h, "handle", h->rollout_on, mwb_rollout_enable);
     if (h->learner_on) return set_err(MWB_ESTATE, "mwb_rollout_learner_enable: already enabled");
     USE_DEVICE(h->cfg.device);
     const size_t N = (size_t)h->rollout.N, T = (size_t)h->rollout.T, T1 = T + 1;
     MwbLearner l = {};
-    int rc = MWB_OK;
-    auto get = [&](auto *&p, size_t bytes) {
-        if (rc != MWB_OK) return;
-        void *q = nullptr;
-        hipError_t e = hipMalloc(&q, bytes);
-        if (e != hipSuccess) { rc = set_err(MWB_ENOMEM, std::string("mwb_rollout_learner_enable: hipMalloc failed: ") + hipGetErrorString(e)); return; }
-        p = static_cast<std::remove_reference_t<decltype(p)>>(q);
-        if ((e = hipMemset(q, 0, bytes)) != hipSuccess) rc = set_err(MWB_EHIP, std::string("mwb_rollout_learner_enable: hipMemset failed: ") + hipGetErrorString(e));
-    };
-    get(l.action, T * N * sizeof(int64_t)); get(l.log_prob, T * N * sizeof(float)); get(l.value, T1 * N * sizeof(float));
-    get(l.taken, T * N * sizeof(int32_t)); get(l.ret, T1 * N * sizeof(float)); get(l.adv, T * N * sizeof(float));
-    get(l.psi_ret, T1 * N * 2 * sizeof(float));
-    // a transition is one sub-step until a push says otherwise
-    if (rc == MWB_OK && hipMemsetD32((hipDeviceptr_t)l.taken, 1, T * N) != hipSuccess) rc = set_err(MWB_EHIP, "mwb_rollout_learner_enable: hipMemsetD32 failed");
-    if (rc == MWB_OK && hipDeviceSynchronize() != hipSuccess) rc = set_err(MWB_EHIP, "mwb_rollout_learner_enable: hipDeviceSynchronize failed");
-    if (rc != MWB_OK) { learner_free(l); return rc; }   // the handle is as it was
+    AllocScope scope(h);
+    int rc = dev_alloc(h, &l.action, T * N);
+    if (!rc) rc = dev_alloc(h, &l.log_prob, T * N);
+    if (!rc) rc = dev_alloc(h, &l.value, T1 * N);
+    if (!rc) rc = dev_alloc(h, &l.taken, T * N);
+    if (!rc) rc = dev_alloc(h, &l.ret, T1 * N);
+    if (!rc) rc = dev_alloc(h, &l.adv, T * N);
+    if (!rc) rc = dev_alloc(h, &l.psi_ret, T1 * N * 2);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetD32((hipDeviceptr_t)l.taken, 1, T * N));   // a transition is one sub-step until a push says otherwise
+    HIP_TRY(hipDeviceSynchronize());
+    scope.keep();
     h->learner = l; h->learner_on = true;
     return MWB_OK;
 }
 
 extern "C" int mwb_rollout_learner_info(mwb_handle *h, struct mwb_rollout_learner_info *out) {
-    if (!h || !out) return set_err(MWB_EINVAL, "mwb_rollout_learner_info: null argument");
-    if (!h->learner_on) return set_err(MWB_ESTATE, "mwb_rollout_learner_info: call mwb_rollout_learner_enable first");
+    NEED(h && out, "argument", h->learner_on, mwb_rollout_learner_enable);
     const MwbLearner &l = h->learner;
     const size_t N = (size_t)h->rollout.N, T = (size_t)h->rollout.T, T1 = T + 1;
     memset(out, 0, sizeof(*out));
@@ -1214,8 +1206,7 @@ extern "C" int mwb_rollout_learner_info(mwb_handle *h, struct mwb_rollout_learne
 
 extern "C" int mwb_rollout_insert(mwb_handle *h, const int64_t *action_dev, const int32_t *action_i32_dev, const float *log_prob_dev,
                                   const float *value_dev, void *stream) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_insert: null handle");
-    if (!h->learner_on) return set_err(MWB_ESTATE, "mwb_rollout_insert: call mwb_rollout_learner_enable first");
+    NEED(h, "handle", h->learner_on, mwb_rollout_learner_enable);
     if (action_dev && action_i32_dev) return set_err(MWB_EINVAL, "mwb_rollout_insert: at most one of action / action_i32 may be given");
     const MwbRollout &r = h->rollout;
     if (r.cursor < 1) return set_err(MWB_ESTATE, "mwb_rollout_insert: no transition has been pushed in this window yet");
@@ -1227,8 +1218,7 @@ extern "C" int mwb_rollout_insert(mwb_handle *h, const int64_t *action_dev, cons
 
 extern "C" int mwb_rollout_returns(mwb_handle *h, int mode, double gamma, double tau, const float *next_value_dev, const float *next_psi_dev,
                                    const float *reward_override_dev, void *stream) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_returns: null handle");
-    if (!h->learner_on) return set_err(MWB_ESTATE, "mwb_rollout_returns: call mwb_rollout_learner_enable first");
+    NEED(h, "handle", h->learner_on, mwb_rollout_learner_enable);
     if (mode != MWB_RETURNS_DISCOUNTED && mode != MWB_RETURNS_GAE && mode != MWB_RETURNS_PSI) return set_err(MWB_EINVAL, "mwb_rollout_returns: unknown mode");
     const MwbRollout &r = h->rollout;
     if (r.cursor != r.T) return set_err(MWB_ESTATE, "mwb_rollout_returns: the rollout does not hold num_steps steps yet");
@@ -1243,8 +1233,7 @@ extern "C" int mwb_rollout_returns(mwb_handle *h, int mode, double gamma, double
 
 extern "C" int mwb_rollout_gather_cols(mwb_handle *h, const int64_t *index_dev, int count, const float *adv_src_dev, float *out_f32_dev,
                                        int64_t *out_action_dev, void *stream) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_rollout_gather_cols: null handle");
-    if (!h->learner_on) return set_err(MWB_ESTATE, "mwb_rollout_gather_cols: call mwb_rollout_learner_enable first");
+    NEED(h, "handle", h->learner_on, mwb_rollout_learner_enable);
     if (count < 0) return set_err(MWB_EINVAL, "mwb_rollout_gather_cols: count < 0");
     if (count == 0) return MWB_OK;
     if (!index_dev || !out_f32_dev || !out_action_dev) return set_err(MWB_EINVAL, "mwb_rollout_gather_cols: null argument");
@@ -1277,6 +1266,7 @@ extern "C" int mwb_terminal_enable(mwb_handle *h, int capacity, unsigned flags) 
     t.rows_float = h->stack ? h->stack_dtype == 1 : (flags & MWB_TERMINAL_FLOAT) != 0;
     t.grey = h->stack && h->stack_cpf == 1;
     const size_t N = (size_t)d.N, rows_bytes = (size_t)capacity * t.nstack * t.cpf * t.plane * (t.rows_float ? 4 : 1);
+    AllocScope scope(h);
     int rc = dev_alloc(h, &t.frames, N * t.plane * 3);
     if (!rc && d.grey) rc = dev_alloc(h, &t.grey_frames, N * t.plane);
     if (!rc) rc = dev_alloc(h, &t.frame_consts, N * d.frame_words);
@@ -1286,18 +1276,18 @@ extern "C" int mwb_terminal_enable(mwb_handle *h, int capacity, unsigned flags) 
     if (!rc) rc = dev_alloc(h, &t.count, (size_t)1);
     if (!rc) rc = dev_alloc(h, &t.dropped, (size_t)1);
     if (!rc) rc = dev_alloc(h, &t.rows, rows_bytes);
-    if (rc) return rc;   // (what was allocated is freed with the handle)
+    if (rc) return rc;
     HIP_TRY(hipMemset(t.row_of, 0xFF, N * sizeof(int32_t)));   // -1: no env has a row
     HIP_TRY(hipMemset(t.row_env, 0xFF, (size_t)capacity * sizeof(int32_t)));
     HIP_TRY(hipDeviceSynchronize());
+    scope.keep();
     h->terminal = t; h->terminal_rows_bytes = rows_bytes; h->terminal_on = true;
     d.end_cause = t.cause;
     return MWB_OK;
 }
 
 extern "C" int mwb_terminal_info(mwb_handle *h, struct mwb_terminal_info *out) {
-    if (!h || !out) return set_err(MWB_EINVAL, "mwb_terminal_info: null argument");
-    if (!h->terminal_on) return set_err(MWB_ESTATE, "mwb_terminal_info: call mwb_terminal_enable first");
+    NEED(h && out, "argument", h->terminal_on, mwb_terminal_enable);
     const MwbTerminal &t = h->terminal;
     memset(out, 0, sizeof(*out));
     out->cause = t.cause; out->frames = t.frames; out->grey = t.grey_frames; out->row_of = t.row_of; out->row_env = t.row_env; out->count = t.count;
@@ -1309,20 +1299,13 @@ extern "C" int mwb_terminal_info(mwb_handle *h, struct mwb_terminal_info *out) {
 }
 
 extern "C" int mwb_terminal_dropped(mwb_handle *h, unsigned long long *envs) {
-    if (!h || !envs) return set_err(MWB_EINVAL, "mwb_terminal_dropped: null argument");
-    *envs = 0;
-    if (!h->terminal_on) return set_err(MWB_ESTATE, "mwb_terminal_dropped: call mwb_terminal_enable first");
-    USE_DEVICE(h->cfg.device);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(envs, h->terminal.dropped, sizeof(*envs), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(h->terminal.dropped, 0, sizeof(*envs)));
-    HIP_TRY(hipDeviceSynchronize());
-    return MWB_OK;
+    if (envs) *envs = 0;
+    NEED(h && envs, "argument", h->terminal_on, mwb_terminal_enable);
+    return read_counters(h, envs, h->terminal.dropped, 1);
 }
 
 extern "C" int mwb_rollout_bootstrap(mwb_handle *h, const float *value_rows_dev, double gamma, void *stream) {
-    if (!h || !value_rows_dev) return set_err(MWB_EINVAL, "mwb_rollout_bootstrap: null argument");
-    if (!h->terminal_on) return set_err(MWB_ESTATE, "mwb_rollout_bootstrap: call mwb_terminal_enable first");
+    NEED(h && value_rows_dev, "argument", h->terminal_on, mwb_terminal_enable);
     if (!h->rollout_on) return set_err(MWB_ESTATE, "mwb_rollout_bootstrap: call mwb_rollout_enable first");
     const MwbRollout &r = h->rollout;
     if (r.cursor < 1) return set_err(MWB_ESTATE, "mwb_rollout_bootstrap: no transition has been pushed in this window yet");
@@ -1353,6 +1336,7 @@ extern "C" int mwb_levels_enable(mwb_handle *h, int64_t num_levels, uint64_t sta
     v.N = h->dev.N; v.L = num_levels; v.start_level = start_level; v.env_offset = env_offset; v.env_stride = env_stride;
     const size_t N = (size_t)v.N, L = (size_t)num_levels;
     uint64_t *seeds = nullptr; uint32_t *base = nullptr;
+    AllocScope scope(h);
     int rc = dev_alloc(h, &base, (size_t)624);
     if (!rc && level_seeds_host) rc = dev_alloc(h, &seeds, L);
     if (!rc) rc = dev_alloc(h, &v.params, (size_t)2);
@@ -1361,7 +1345,7 @@ extern "C" int mwb_levels_enable(mwb_handle *h, int64_t num_levels, uint64_t sta
     if (!rc) rc = dev_alloc(h, &v.episode_no, N);
     if (!rc) rc = dev_alloc(h, &v.rejected, (size_t)1);
     if (!rc && (flags & MWB_LEVELS_TALLY)) rc = dev_alloc(h, &v.tallies, 3 * L);
-    if (rc) return rc;   // (what was allocated is freed with the handle)
+    if (rc) return rc;
     uint32_t base_host[624];
     mwb_levels_mt_base(base_host);   // the constant first loop of init_by_array: once, here
     const uint64_t params[2] = {(uint64_t)mode, sampler_seed};
@@ -1372,6 +1356,7 @@ extern "C" int mwb_levels_enable(mwb_handle *h, int64_t num_levels, uint64_t sta
     HIP_TRY(hipMemset(v.index, 0xFF, 2 * N * sizeof(int32_t)));    // -1: no level yet, no previous one
     HIP_TRY(hipMemset(v.next_level, 0xFF, N * sizeof(int32_t)));   // -1: no request
     HIP_TRY(hipDeviceSynchronize());
+    scope.keep();
     v.base = base; v.seeds = seeds;
     h->levels = v; h->levels_mode = mode; h->levels_sampler_seed = sampler_seed; h->levels_flags = flags; h->levels_on = true;
     h->seeded = true;   // every env is given a stream before it is generated
@@ -1379,8 +1364,7 @@ extern "C" int mwb_levels_enable(mwb_handle *h, int64_t num_levels, uint64_t sta
 }
 
 extern "C" int mwb_levels_restart(mwb_handle *h, int mode, uint64_t sampler_seed, int clear_tally, void *stream) {
-    if (!h) return set_err(MWB_EINVAL, "mwb_levels_restart: null handle");
-    if (!h->levels_on) return set_err(MWB_ESTATE, "mwb_levels_restart: call mwb_levels_enable first");
+    NEED(h, "handle", h->levels_on, mwb_levels_enable);
     if (mode != MWB_LEVELS_SEQUENTIAL && mode != MWB_LEVELS_UNIFORM && mode != MWB_LEVELS_TABLE) return set_err(MWB_EINVAL, "mwb_levels_restart: unknown mode");
     USE_DEVICE(h->cfg.device);
     mwb_launch_levels_restart(h->levels, mode, sampler_seed, clear_tally != 0, (hipStream_t)stream);
@@ -1390,8 +1374,7 @@ extern "C" int mwb_levels_restart(mwb_handle *h, int mode, uint64_t sampler_seed
 }
 
 extern "C" int mwb_levels_info(mwb_handle *h, struct mwb_levels_info *out) {
-    if (!h || !out) return set_err(MWB_EINVAL, "mwb_levels_info: null argument");
-    if (!h->levels_on) return set_err(MWB_ESTATE, "mwb_levels_info: call mwb_levels_enable first");
+    NEED(h && out, "argument", h->levels_on, mwb_levels_enable);
     const MwbLevels &v = h->levels;
     memset(out, 0, sizeof(*out));
     out->index = v.index; out->prev_index = v.prev_index; out->next_level = v.next_level; out->episode_no = v.episode_no;
@@ -1403,15 +1386,9 @@ extern "C" int mwb_levels_info(mwb_handle *h, struct mwb_levels_info *out) {
 }
 
 extern "C" int mwb_levels_rejected(mwb_handle *h, unsigned long long *entries) {
-    if (!h || !entries) return set_err(MWB_EINVAL, "mwb_levels_rejected: null argument");
-    *entries = 0;
-    if (!h->levels_on) return set_err(MWB_ESTATE, "mwb_levels_rejected: call mwb_levels_enable first");
-    USE_DEVICE(h->cfg.device);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(entries, h->levels.rejected, sizeof(*entries), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(h->levels.rejected, 0, sizeof(*entries)));
-    HIP_TRY(hipDeviceSynchronize());
-    return MWB_OK;
+    if (entries) *entries = 0;
+    NEED(h && entries, "argument", h->levels_on, mwb_levels_enable);
+    return read_counters(h, entries, h->levels.rejected, 1);
 }
 
 // ------------------------------------------------------------------------------ copying environments
@@ -1493,10 +1470,11 @@ extern "C" int mwb_copy_envs(mwb_handle *dst, const int32_t *dst_idx_dev, mwb_ha
         rc = dev_alloc(dst, &dst->copy_rejected, (size_t)1); if (rc) return rc;
         HIP_TRY(hipDeviceSynchronize());   // the scratch is zero before a kernel on the caller's stream counts in it
     }
-    if (dst->copy_pairs_cap < (size_t)count) {   // (hipFree waits for the kernels still reading the old one)
-        if (dst->copy_pairs) { HIP_TRY(hipFree(dst->copy_pairs)); dst->copy_pairs = nullptr; dst->copy_pairs_cap = 0; }
+    if (dst->copy_pairs_cap < (size_t)count) {
         const size_t cap = (size_t)count < (size_t)d.N ? (size_t)d.N : (size_t)count;
-        HIP_TRY(hipMalloc((void **)&dst->copy_pairs, cap * sizeof(int2)));
+        dst->copy_pairs_cap = 0;
+        rc = dev_realloc(dst, &dst->copy_pairs, cap); if (rc) return rc;
+        HIP_TRY(hipDeviceSynchronize());   // its zeroes are down before a kernel on the caller's stream writes it
         dst->copy_pairs_cap = cap;
     }
     const int slot = copy_table_for(dst, src);
@@ -1542,13 +1520,7 @@ extern "C" int mwb_copy_envs(mwb_handle *dst, const int32_t *dst_idx_dev, mwb_ha
 extern "C" int mwb_copy_rejected(mwb_handle *dst, unsigned long long *pairs) {
     if (!dst || !pairs) return set_err(MWB_EINVAL, "mwb_copy_rejected: null argument");
     *pairs = 0;
-    if (!dst->copy_rejected) return MWB_OK;   // no copy yet
-    USE_DEVICE(dst->cfg.device);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(pairs, dst->copy_rejected, sizeof(*pairs), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(dst->copy_rejected, 0, sizeof(*pairs)));
-    HIP_TRY(hipDeviceSynchronize());
-    return MWB_OK;
+    return dst->copy_rejected ? read_counters(dst, pairs, dst->copy_rejected, 1) : MWB_OK;   // (no copy yet: nothing to read)
 }
 
 // bytes of per-env state one accepted pair of a copy from src into dst moves (the descriptor table's total); for measurements
@@ -1562,240 +1534,58 @@ extern "C" long long mwb_copy_env_bytes(mwb_handle *dst, mwb_handle *src) {
 }
 
 // -------------------------------------------------------------------------------- introspection
-template <typename T>
-static int fetch(T *dst, const T *src_dev, size_t first, size_t count, size_t stride) {
-    if (!dst) return MWB_OK;
-    HIP_TRY(hipMemcpy(dst, src_dev + first * stride, count * stride * sizeof(T), hipMemcpyDeviceToHost));
-    return MWB_OK;
-}
-
 extern "C" int mwb_num_boxes(mwb_handle *h) { return h ? h->dev.n_boxes : 0; }
 extern "C" int mwb_room_words(mwb_handle *h) { return h ? h->dev.room_words : 0; }
 
-// box arrays live as [B][N] planes on the device and as [count][B](x width) rows in mwb_state
-static int fetch_boxes(double *dst, const double *src_dev, size_t N, int B, size_t first, size_t count, size_t width) {
-    if (!dst) return MWB_OK;
-    std::vector<double> plane(count * width);
-    for (int b = 0; b < B; b++) {
-        HIP_TRY(hipMemcpy(plane.data(), src_dev + ((size_t)b * N + first) * width, count * width * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < count; i++)
-            for (size_t k = 0; k < width; k++) dst[(i * B + b) * width + k] = plane[i * width + k];
-    }
+// mwb_state <-> the device arrays.  The list of fields, the moves between the two layouts and everything mwb_set_state refuses
+// are mwb_state_fields.h; this file gives them hipMemcpy.  All four functions are synchronous.
+static int dev_move(void *dst, const void *src, size_t bytes, bool to_device) {
+    HIP_TRY(hipMemcpy(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
     return MWB_OK;
 }
-static int store_boxes(const double *src, double *dst_dev, size_t N, int B, size_t first, size_t count, size_t width) {
-    if (!src) return MWB_OK;
-    std::vector<double> plane(count * width);
-    for (int b = 0; b < B; b++) {
-        for (size_t i = 0; i < count; i++)
-            for (size_t k = 0; k < width; k++) plane[i * width + k] = src[(i * B + b) * width + k];
-        HIP_TRY(hipMemcpy(dst_dev + ((size_t)b * N + first) * width, plane.data(), count * width * sizeof(double), hipMemcpyHostToDevice));
-    }
-    return MWB_OK;
-}
-template <typename T>
-static int store(const T *src, T *dst_dev, size_t first, size_t count, size_t stride) {
-    if (!src) return MWB_OK;
-    HIP_TRY(hipMemcpy(dst_dev + first * stride, src, count * stride * sizeof(T), hipMemcpyHostToDevice));
-    return MWB_OK;
+#define STATE_RANGE(first, count) \
+    if (first < 0 || count < 0 || first + count > h->dev.N) return set_err(MWB_EINVAL, std::string(__func__) + ": env range out of bounds")
+// the stores of the setters, after whatever each of them refuses: the cached frames of the range no longer show its state
+// (invalidated first: an error half-way leaves no stale frame trusted).  The caller has synchronised and holds the device guard.
+static int put_state(mwb_handle *h, int first, int count, const mwb_state &in) {
+    if (int rc = invalidate_frames(h, first, count)) return rc;
+    return mwb_state_put(h->dev, first, count, &in, dev_move);
 }
 
 extern "C" int mwb_get_state(mwb_handle *h, int first, int count, mwb_state *o) {
     if (!h || !o) return set_err(MWB_EINVAL, "mwb_get_state: null argument");
-    const MwbDev &d = h->dev;
-    if (first < 0 || count < 0 || first + count > d.N) return set_err(MWB_EINVAL, "mwb_get_state: env range out of bounds");
+    STATE_RANGE(first, count);
     USE_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize());
-    const size_t N = (size_t)d.N;
-    const int B = d.n_boxes;
-    std::vector<double> a(count), b(count);
-    int rc;
-    if (o->agent_pos) {
-        if ((rc = fetch(a.data(), d.agent_x, first, count, 1))) return rc;
-        if ((rc = fetch(b.data(), d.agent_z, first, count, 1))) return rc;
-        for (int i = 0; i < count; i++) { o->agent_pos[i * 3] = a[i]; o->agent_pos[i * 3 + 1] = 0.0; o->agent_pos[i * 3 + 2] = b[i]; }
-    }
-    if (o->box_pos) {
-        std::vector<double> bx((size_t)count * B), bz((size_t)count * B), by((size_t)count * B);
-        if ((rc = fetch_boxes(bx.data(), d.box_x, N, B, first, count, 1))) return rc;
-        if ((rc = fetch_boxes(bz.data(), d.box_z, N, B, first, count, 1))) return rc;
-        if ((rc = fetch_boxes(by.data(), d.box_y, N, B, first, count, 1))) return rc;
-        for (size_t i = 0; i < (size_t)count * B; i++) { o->box_pos[i * 3] = bx[i]; o->box_pos[i * 3 + 1] = by[i]; o->box_pos[i * 3 + 2] = bz[i]; }
-    }
-    if ((rc = fetch(o->agent_dir, d.agent_dir, first, count, 1))) return rc;
-    if ((rc = fetch_boxes(o->box_dir, d.box_dir, N, B, first, count, 1))) return rc;
-    if ((rc = fetch_boxes(o->box_color, d.box_color, N, B, first, count, 3))) return rc;
-    if ((rc = fetch_boxes(o->box_size, d.box_size, N, B, first, count, 1))) return rc;
-    if ((rc = fetch(o->goal_dist, d.goal_dist, first, count, 1))) return rc;
-    if ((rc = fetch(o->carrying, d.carrying, first, count, 1))) return rc;
-    if (o->ent_meta || o->ent_radius || o->ent_height || o->ent_scale || o->ent_order || o->task_f || o->task_i || o->text_tex) {
-        if (!d.ent_task) return set_err(MWB_EINVAL, "mwb_get_state: entity-list fields exist for the tasks >= MWB_TASK_PICKUPOBJS only");
-        if (o->ent_meta) {
-            std::vector<int32_t> plane(count);
-            for (int b = 0; b < B; b++) {
-                HIP_TRY(hipMemcpy(plane.data(), d.ent_meta + (size_t)b * N + first, count * sizeof(int32_t), hipMemcpyDeviceToHost));
-                for (int i = 0; i < count; i++) o->ent_meta[(size_t)i * B + b] = plane[i];
-            }
-        }
-        if ((rc = fetch_boxes(o->ent_radius, d.ent_radius, N, B, first, count, 1))) return rc;
-        if ((rc = fetch_boxes(o->ent_height, d.ent_height, N, B, first, count, 1))) return rc;
-        if ((rc = fetch_boxes(o->ent_scale, d.ent_scale, N, B, first, count, 1))) return rc;
-        if (o->ent_order) {
-            std::vector<uint8_t> ord((size_t)count * MWB_ORDER_STRIDE);
-            std::vector<int32_t> no(count);
-            HIP_TRY(hipMemcpy(ord.data(), d.ent_order + (size_t)first * MWB_ORDER_STRIDE, ord.size(), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(no.data(), d.n_order + first, count * sizeof(int32_t), hipMemcpyDeviceToHost));
-            for (int i = 0; i < count; i++)
-                for (int k = 0; k <= B; k++) {
-                    const int v = ord[(size_t)i * MWB_ORDER_STRIDE + k];
-                    o->ent_order[(size_t)i * (B + 1) + k] = k >= no[i] ? -1 : (v == MWB_ENT_AGENT ? -2 : v);
-                }
-        }
-        if ((rc = fetch(o->task_f, d.task_f, first, count, 1))) return rc;
-        if ((rc = fetch(o->task_i, d.task_i, first, count, 1))) return rc;
-        if ((rc = fetch(o->text_tex, d.text_tex, first, count, 8))) return rc;
-    }
-    if ((rc = fetch(o->goal_idx, d.goal_idx, first, count, 1))) return rc;
-    if ((rc = fetch(o->episode_count, d.episode_count, first, count, 1))) return rc;
-    if ((rc = fetch(o->task_step_count, d.task_step_count, first, count, 1))) return rc;
-    if ((rc = fetch(o->cam, d.cam, first, count, 4))) return rc;
-    if ((rc = fetch(o->sky_color, d.sky_color, first, count, 3))) return rc;
-    if ((rc = fetch(o->light_pos, d.light_pos, first, count, 3))) return rc;
-    if ((rc = fetch(o->light_color, d.light_color, first, count, 3))) return rc;
-    if ((rc = fetch(o->light_ambient, d.light_ambient, first, count, 3))) return rc;
-    if ((rc = fetch(o->step_count, d.step_count, first, count, 1))) return rc;
-    if ((rc = fetch(o->n_rooms, d.n_rooms, first, count, 1))) return rc;
-    if ((rc = fetch(o->n_segs, d.n_segs, first, count, 1))) return rc;
-    if (o->rng_pos || o->rng_keysum || o->rng_state) {
-        std::vector<uint32_t> st((size_t)count * MWB_MT_WORDS);
-        if ((rc = fetch(st.data(), d.rng, first, count, MWB_MT_WORDS))) return rc;
-        for (int i = 0; i < count; i++) {
-            uint64_t sum = 0;
-            for (int k = 0; k < 624; k++) sum += st[(size_t)i * MWB_MT_WORDS + k];
-            if (o->rng_keysum) o->rng_keysum[i] = (uint32_t)(sum & 0xFFFFFFFFu);
-            if (o->rng_pos) o->rng_pos[i] = (int32_t)st[(size_t)i * MWB_MT_WORDS + 624];
-        }
-        if (o->rng_state) memcpy(o->rng_state, st.data(), st.size() * sizeof(uint32_t));
-    }
-    return MWB_OK;
+    std::string why;
+    const int rc = mwb_state_get(h->dev, first, count, o, dev_move, &why);
+    return why.empty() ? rc : set_err(rc, why);
 }
 
 extern "C" int mwb_set_state(mwb_handle *h, int first, int count, const mwb_state *in) {
     if (!h || !in) return set_err(MWB_EINVAL, "mwb_set_state: null argument");
-    const MwbDev &d = h->dev;
-    if (first < 0 || count < 0 || first + count > d.N) return set_err(MWB_EINVAL, "mwb_set_state: env range out of bounds");
-    if (in->goal_idx)
-        for (int i = 0; i < count; i++)
-            if (in->goal_idx[i] < 0 || in->goal_idx[i] > 1) return set_err(MWB_EINVAL, "mwb_set_state: goal_idx must be 0 or 1");
-    if (in->carrying)
-        for (int i = 0; i < count; i++)
-            if (in->carrying[i] < -1 || in->carrying[i] >= h->dev.n_boxes) return set_err(MWB_EINVAL, "mwb_set_state: carrying must be -1 or a box index");
-    if (in->rng_state)
-        for (int i = 0; i < count; i++)
-            if (in->rng_state[(size_t)i * MWB_MT_WORDS + 624] > 624u) return set_err(MWB_EINVAL, "mwb_set_state: MT19937 position must be 0..624");
-    {   // poses, sizes and camera parameters go straight into the step and render kernels: no NaN / inf, no empty boxes
-        auto finite = [](const double *v, size_t n) { if (v) for (size_t i = 0; i < n; i++) if (!std::isfinite(v[i])) return false; return true; };
-        const size_t c = (size_t)count, B_ = (size_t)h->dev.n_boxes;
-        if (!finite(in->agent_pos, c * 3) || !finite(in->agent_dir, c) || !finite(in->box_pos, c * B_ * 3) || !finite(in->box_dir, c * B_) ||
-            !finite(in->box_color, c * B_ * 3) || !finite(in->box_size, c * B_) || !finite(in->cam, c * 4) || !finite(in->sky_color, c * 3) ||
-            !finite(in->light_pos, c * 3) || !finite(in->light_color, c * 3) || !finite(in->light_ambient, c * 3) || !finite(in->goal_dist, c))
-            return set_err(MWB_EINVAL, "mwb_set_state: non-finite value");
-        if (in->box_size)
-            for (size_t i = 0; i < c * B_; i++)
-                if (!(in->box_size[i] > 0)) return set_err(MWB_EINVAL, "mwb_set_state: box_size must be > 0");
-    }
+    STATE_RANGE(first, count);
     USE_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize());
-    const size_t N = (size_t)d.N;
-    const int B = d.n_boxes;
-    int rc;
-    if ((rc = invalidate_frames(h, first, count))) return rc;   // first: an error half-way leaves no stale frame trusted
-    if (in->agent_pos) {
-        std::vector<double> a(count), b(count);
-        for (int i = 0; i < count; i++) { a[i] = in->agent_pos[i * 3]; b[i] = in->agent_pos[i * 3 + 2]; }
-        if ((rc = store(a.data(), d.agent_x, first, count, 1))) return rc;
-        if ((rc = store(b.data(), d.agent_z, first, count, 1))) return rc;
-    }
-    if (in->box_pos) {
-        std::vector<double> bx((size_t)count * B), bz((size_t)count * B), by((size_t)count * B);
-        for (size_t i = 0; i < (size_t)count * B; i++) { bx[i] = in->box_pos[i * 3]; by[i] = in->box_pos[i * 3 + 1]; bz[i] = in->box_pos[i * 3 + 2]; }
-        if ((rc = store_boxes(bx.data(), d.box_x, N, B, first, count, 1))) return rc;
-        if ((rc = store_boxes(by.data(), d.box_y, N, B, first, count, 1))) return rc;
-        if ((rc = store_boxes(bz.data(), d.box_z, N, B, first, count, 1))) return rc;
-    }
-    if ((rc = store(in->agent_dir, d.agent_dir, first, count, 1))) return rc;
-    if ((rc = store_boxes(in->box_dir, d.box_dir, N, B, first, count, 1))) return rc;
-    if ((rc = store_boxes(in->box_color, d.box_color, N, B, first, count, 3))) return rc;
-    if ((rc = store_boxes(in->box_size, d.box_size, N, B, first, count, 1))) return rc;
-    if ((rc = store(in->goal_dist, d.goal_dist, first, count, 1))) return rc;
-    if ((rc = store(in->carrying, d.carrying, first, count, 1))) return rc;
-    if (in->ent_meta || in->ent_radius || in->ent_height || in->ent_scale || in->ent_order || in->task_f || in->task_i || in->text_tex) {
-        if (!d.ent_task) return set_err(MWB_EINVAL, "mwb_set_state: entity-list fields exist for the tasks >= MWB_TASK_PICKUPOBJS only");
-        if (in->ent_radius || in->ent_height || in->ent_scale || in->text_tex) return set_err(MWB_EINVAL, "mwb_set_state: ent_radius / ent_height / ent_scale / text_tex are read-only");
-        if (in->ent_meta) {   // only the `alive` bit may differ (an entity PickupObjs removed): kinds and dimensions belong to the episode
-            std::vector<int32_t> plane(count);
-            for (int b = 0; b < B; b++) {
-                HIP_TRY(hipMemcpy(plane.data(), d.ent_meta + (size_t)b * N + first, count * sizeof(int32_t), hipMemcpyDeviceToHost));
-                for (int i = 0; i < count; i++) {
-                    const int32_t v = in->ent_meta[(size_t)i * B + b];
-                    if ((v & ~(1 << 9)) != (plane[i] & ~(1 << 9))) return set_err(MWB_EINVAL, "mwb_set_state: ent_meta may only change an entity's alive bit");
-                    plane[i] = v;
-                }
-                HIP_TRY(hipMemcpy(d.ent_meta + (size_t)b * N + first, plane.data(), count * sizeof(int32_t), hipMemcpyHostToDevice));
-            }
-        }
-        if (in->ent_order) {
-            std::vector<uint8_t> ord((size_t)count * MWB_ORDER_STRIDE, (uint8_t)MWB_ENT_AGENT);
-            std::vector<int32_t> no(count);
-            for (int i = 0; i < count; i++) {
-                int n = 0;
-                uint32_t seen = 0;
-                for (int k = 0; k <= B; k++) {
-                    const int v = in->ent_order[(size_t)i * (B + 1) + k];
-                    if (v == -1) break;
-                    if (v != -2 && (v < 0 || v >= B)) return set_err(MWB_EINVAL, "mwb_set_state: ent_order entries are slots, -2 (the agent) or -1 (end)");
-                    const uint32_t bit = 1u << (v == -2 ? 31 : v);
-                    if (seen & bit) return set_err(MWB_EINVAL, "mwb_set_state: ent_order lists an entity twice");
-                    seen |= bit;
-                    ord[(size_t)i * MWB_ORDER_STRIDE + n++] = (uint8_t)(v == -2 ? MWB_ENT_AGENT : v);
-                }
-                no[i] = n;
-            }
-            HIP_TRY(hipMemcpy(d.ent_order + (size_t)first * MWB_ORDER_STRIDE, ord.data(), ord.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d.n_order + first, no.data(), count * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        if ((rc = store(in->task_f, d.task_f, first, count, 1))) return rc;
-        if ((rc = store(in->task_i, d.task_i, first, count, 1))) return rc;
-    }
-    if ((rc = store(in->goal_idx, d.goal_idx, first, count, 1))) return rc;
-    if ((rc = store(in->episode_count, d.episode_count, first, count, 1))) return rc;
-    if ((rc = store(in->task_step_count, d.task_step_count, first, count, 1))) return rc;
-    if ((rc = store(in->cam, d.cam, first, count, 4))) return rc;
-    if ((rc = store(in->sky_color, d.sky_color, first, count, 3))) return rc;
-    if ((rc = store(in->light_pos, d.light_pos, first, count, 3))) return rc;
-    if ((rc = store(in->light_color, d.light_color, first, count, 3))) return rc;
-    if ((rc = store(in->light_ambient, d.light_ambient, first, count, 3))) return rc;
-    if ((rc = store(in->step_count, d.step_count, first, count, 1))) return rc;
-    if ((rc = store(in->rng_state, d.rng, first, count, MWB_MT_WORDS))) return rc;
-    return MWB_OK;
+    std::string why;   // a refused call changes nothing: every check comes before the first store
+    if (int rc = mwb_state_check(h->dev, first, count, in, dev_move, &why)) return why.empty() ? rc : set_err(rc, why);
+    return put_state(h, first, count, *in);
 }
 
 extern "C" int mwb_set_agent(mwb_handle *h, int first, int count, const double *pos_xz, const double *dir, const int32_t *step_count) {
     if (!h) return set_err(MWB_EINVAL, "mwb_set_agent: null handle");
-    const MwbDev &d = h->dev;
-    if (first < 0 || count < 0 || first + count > d.N) return set_err(MWB_EINVAL, "mwb_set_agent: env range out of bounds");
+    STATE_RANGE(first, count);
     USE_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = invalidate_frames(h, first, count)) return rc;
+    std::vector<double> pos;
+    mwb_state st = {};
     if (pos_xz) {
-        std::vector<double> a(count), b(count);
-        for (int i = 0; i < count; i++) { a[i] = pos_xz[i * 2]; b[i] = pos_xz[i * 2 + 1]; }
-        HIP_TRY(hipMemcpy(d.agent_x + first, a.data(), count * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d.agent_z + first, b.data(), count * sizeof(double), hipMemcpyHostToDevice));
+        pos.assign((size_t)count * 3, 0.0);
+        for (int i = 0; i < count; i++) { pos[(size_t)i * 3] = pos_xz[i * 2]; pos[(size_t)i * 3 + 2] = pos_xz[i * 2 + 1]; }
+        st.agent_pos = pos.data();
     }
-    if (dir) HIP_TRY(hipMemcpy(d.agent_dir + first, dir, count * sizeof(double), hipMemcpyHostToDevice));
-    if (step_count) HIP_TRY(hipMemcpy(d.step_count + first, step_count, count * sizeof(int32_t), hipMemcpyHostToDevice));
-    return MWB_OK;
+    st.agent_dir = const_cast<double *>(dir); st.step_count = const_cast<int32_t *>(step_count);
+    return put_state(h, first, count, st);
 }
 
 extern "C" int mwb_num_textures(mwb_handle *h) { return h ? h->dev.n_tex : 0; }
@@ -1818,22 +1608,13 @@ extern "C" int mwb_debug_wg_times(mwb_handle *h, unsigned long long *out, int ma
 extern "C" int mwb_debug_counters(mwb_handle *h, unsigned long long *out8, int reset) {
     if (!h || !out8) return set_err(MWB_EINVAL, "mwb_debug_counters: null argument");
     if (!h->dev.dbg_counters) return set_err(MWB_ESTATE, "mwb_debug_counters: create the handle with MWB_EXP bit 2 set");
-    USE_DEVICE(h->cfg.device);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out8, h->dev.dbg_counters, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (reset) HIP_TRY(hipMemset(h->dev.dbg_counters, 0, 8 * sizeof(unsigned long long)));
-    return MWB_OK;
+    return read_counters(h, out8, h->dev.dbg_counters, 8, reset != 0);
 }
 
 /* frames the step passes (mwb_step / mwb_step_i64) took from the last-frame cache / rendered since the last call */
 extern "C" int mwb_frame_reuse_stats(mwb_handle *h, unsigned long long out[2]) {
     if (!h || !out) return set_err(MWB_EINVAL, "mwb_frame_reuse_stats: null argument");
-    USE_DEVICE(h->cfg.device);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, h->dev.reuse_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset(h->dev.reuse_stats, 0, 2 * sizeof(unsigned long long)));
-    HIP_TRY(hipDeviceSynchronize());
-    return MWB_OK;
+    return read_counters(h, out, h->dev.reuse_stats, 2);
 }
 
 /* which kernel a step's bulk render launch of this handle runs now: 0 generic (render_kernel / render_grey_kernel), 1 render_fixed_kernel */
@@ -1854,19 +1635,15 @@ extern "C" int mwb_set_domain_rand(mwb_handle *h, int domain_rand) {
 extern "C" int mwb_set_task_state(mwb_handle *h, int first, int count, const int64_t *episode_count, const int64_t *task_step_count,
                                   const int32_t *goal_idx) {
     if (!h) return set_err(MWB_EINVAL, "mwb_set_task_state: null handle");
-    const MwbDev &d = h->dev;
-    if (first < 0 || count < 0 || first + count > d.N) return set_err(MWB_EINVAL, "mwb_set_task_state: env range out of bounds");
+    STATE_RANGE(first, count);
+    for (int i = 0; goal_idx && i < count; i++)
+        if (goal_idx[i] < 0 || goal_idx[i] > 1) return set_err(MWB_EINVAL, "mwb_set_task_state: goal_idx must be 0 or 1");
     USE_DEVICE(h->cfg.device);
     HIP_TRY(hipDeviceSynchronize());
-    if (int rc = invalidate_frames(h, first, count)) return rc;
-    if (episode_count) HIP_TRY(hipMemcpy(d.episode_count + first, episode_count, count * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (task_step_count) HIP_TRY(hipMemcpy(d.task_step_count + first, task_step_count, count * sizeof(int64_t), hipMemcpyHostToDevice));
-    if (goal_idx) {
-        for (int i = 0; i < count; i++)
-            if (goal_idx[i] < 0 || goal_idx[i] > 1) return set_err(MWB_EINVAL, "mwb_set_task_state: goal_idx must be 0 or 1");
-        HIP_TRY(hipMemcpy(d.goal_idx + first, goal_idx, count * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    return MWB_OK;
+    mwb_state st = {};
+    st.episode_count = const_cast<int64_t *>(episode_count); st.task_step_count = const_cast<int64_t *>(task_step_count);
+    st.goal_idx = const_cast<int32_t *>(goal_idx);
+    return put_state(h, first, count, st);
 }
 
 extern "C" int mwb_intersect(mwb_handle *h, int env, int ent, double x, double z, double radius, int *result) {

@@ -188,7 +188,9 @@ typedef struct mwb_state {
 /* replaces: gym.make('MiniWorld-<Class>-v0') x N + SubprocVecEnv.__init__
  * (envs/__init__.py:43-49, pytorch-a2c-ppo-acktr/envs.py:57-63, vec_env/subproc_vec_env.py:36-56) */
 int mwb_create(const mwb_config *cfg, mwb_handle **out);
-/* replaces: SubprocVecEnv.close (vec_env/subproc_vec_env.py:87-97) */
+/* replaces: SubprocVecEnv.close (vec_env/subproc_vec_env.py:87-97).  Frees everything the handle allocated, the buffers of
+ * every mwb_*_enable below included.  Each of those functions either succeeds or leaves the handle as it was: what it had
+ * allocated before a failure (MWB_ENOMEM, MWB_EHIP) is freed again, and the call can be repeated. */
 int mwb_destroy(mwb_handle *h);
 const char *mwb_last_error(void);
 int mwb_abi_version(void);
